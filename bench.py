@@ -17,8 +17,13 @@ Workloads (BASELINE.json configs):
     c5  3840x2160, 256 spot lights per GPU, independent replicas, no collective
 
 Prints ONE JSON line on rank 0 (see the repo contract), with `roofline` for the dominant
-kernel of the run (its longest pass) and `cpu_baseline` (the scalar oracle timed on this box's
-cores: all threads, and one thread). `python bench.py --gpus N` without a launcher starts its own N ranks.
+kernel of the run (its longest pass). `python bench.py --gpus N` without a launcher starts its own N ranks.
+
+A plain run sets up, warms up, times --steps frames and prints the line. `--full` adds everything that is not part of
+`value`: `image_checksum`, `cpu_baseline` (the scalar oracle timed on this box's cores: all threads, and one thread), the
+single-GPU extras (LUT reuse, OETF, extension LUTs, G-buffer raster, parity against the SPIR-V vectors, the literal build)
+and the committed strong-scaling reference of the row-tiled run. `--dump-outputs DIR` writes what the last timed step
+computed as float32 .npy files (see dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -67,7 +72,11 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal: every rank renders on cuda:0 (several ranks on a one-GPU box; needs --backend gloo)")
     ap.add_argument("--cpu-rows", type=int, default=540, help="rows of the frame the all-threads CPU baseline shades")
-    ap.add_argument("--no-extras", action="store_true", help="skip the measurements that are not part of `value` (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is not part of `value`: image checksum, CPU baseline, extras, scaling reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
 
     # The contract is ONE JSON line on stdout. Libraries write there too (RCCL prints its version banner to stdout on
@@ -283,6 +292,11 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
 
+    # the RGBA16 image of the last timed frame (rank 0: the composed frame when tiled)
+    final_image = composed if tiled else targets[(args.steps - 1) % len(targets)].color[:H]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final_image, sky)
+
     t = torch.tensor([elapsed], dtype=torch.float64)
     g = torch.tensor([geometry_px_local], dtype=torch.int64)
     if world > 1:
@@ -385,7 +399,7 @@ def main():
                            "achieved_GBps": frame_bytes / frame_s / 1e9, "frac": frame_bytes / frame_s / 1e9 / HBM_PEAK_GBS},
     }
 
-    if tiled:
+    if tiled and args.full:
         # N = 1 of the default run is the 4K workload the metric is quoted on; the strong-scaling base of THIS workload
         # (same 8K frame on one GPU, untiled) is a committed measurement, repeated here so that the speed-up can be read
         # off the line without mixing workloads.
@@ -406,10 +420,10 @@ def main():
         weights = (torch.arange(H, device=img.device, dtype=torch.int64) % 251 + 1).view(H, 1, 1)
         return {"sum": int(img.sum().item()), "row_weighted_sum": int((img * weights).sum().item())}
 
-    if rank == 0:
-        out["image_checksum"] = checksum(composed if tiled else targets[(args.steps - 1) % len(targets)].color[:H])
+    if rank == 0 and args.full:
+        out["image_checksum"] = checksum(final_image)
 
-    extras = world == 1 and not tiled and not args.no_extras
+    extras = args.full and world == 1 and not tiled and not args.no_extras
     if extras:
         # LUT reuse across frames (abi.h szg_skyview_set_lut_reuse; SURVEY 8e: identical results): the steady state of a
         # scene whose atmosphere, sun and camera do not move. NOT part of `value` - the reference recomputes both LUTs every
@@ -559,7 +573,7 @@ def main():
         if os.path.exists(literal):
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(args.steps), "--warmup",
-                                    str(args.warmup), "--no-cpu-baseline", "--no-extras"], env=dict(os.environ, SZG_HIP_LIBRARY=literal),
+                                    str(args.warmup), "--full", "--no-cpu-baseline", "--no-extras"], env=dict(os.environ, SZG_HIP_LIBRARY=literal),
                                    capture_output=True, text=True, timeout=300)
                 lit = json.loads(r.stdout.strip().split("\n")[-1])
                 out["literal_build"] = {"in_value": False, "library": "libszg_hip_literal.so", "ms_per_frame": lit["ms_per_step"],
@@ -569,7 +583,7 @@ def main():
             except Exception as e:  # the extra must never take the bench line down
                 log(f"literal_build extra failed: {e}")
 
-    if rank == 0 and not args.no_cpu_baseline and args.gpus == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and args.gpus == 1:
         out["cpu_baseline"] = cpu_baseline(args, wl, atm, cam, sun, moon, spots, syn)
     if rank == 0:
         log("per-pass device ms:", {k: round(v, 4) for k, v in per.items()})
@@ -588,6 +602,47 @@ def latest_profile(suffix):
 
     found = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_{suffix}")))
     return found[-1] if found else None
+
+
+DUMP_SEED = 20250611
+DUMP_PIXELS = 1 << 20  # colour: at most 16 MiB of float32
+DUMP_LUT_TEXELS = 1 << 21  # per LUT: the 2048 x 1024 sky-view LUT in full (32 MiB)
+DUMP_BYTES_MAX = 64_000_000
+
+
+def _sample_index(n, cap, seed):
+    """None when all `n` texels fit under `cap`; else a fixed, seeded, sorted sample of `cap` indices: one random index in each
+    of `cap` equal strata of [0, n), so that the sample covers the whole image evenly."""
+    if n <= cap:
+        return None
+    edges = np.arange(cap + 1, dtype=np.int64) * n // cap
+    return edges[:-1] + (np.random.RandomState(seed).random_sample(cap) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(directory, image, sky):
+    """What a caller of the timed path receives from its last step, as float32 .npy files in `directory`:
+        color.npy              the RGBA16 UNORM scene colour decoded to [0, 1]: [H, W, 4] when it has at most DUMP_PIXELS
+                               pixels, else the pixels of _sample_index() in row-major order, [DUMP_PIXELS, 4]
+        transmittance_lut.npy  the transmittance LUT, [h, w, 4] (sampled the same way above DUMP_LUT_TEXELS texels)
+        skyview_lut.npy        the sky-view LUT, [h, w, 4] (same)
+    The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    flat = image.reshape(-1, 4)
+    idx = _sample_index(flat.shape[0], DUMP_PIXELS, DUMP_SEED)
+    if idx is None:
+        codes = image.cpu().numpy()
+    else:
+        codes = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    arrays = {"color": codes.view(np.uint16).astype(np.float32) / np.float32(65535.0)}
+    for name, im in (("transmittance_lut", sky.transmittanceLUT()), ("skyview_lut", sky.skyviewLUT())):
+        lut = sky.download_lut(im)
+        idx = _sample_index(lut.shape[0] * lut.shape[1], DUMP_LUT_TEXELS, DUMP_SEED + 1)
+        arrays[name] = lut if idx is None else lut.reshape(-1, 4)[idx]
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {directory}:", {n: list(a.shape) for n, a in arrays.items()}, f"{total / 1e6:.1f} MB")
 
 
 def self_launch(nproc, real_stdout):

@@ -25,17 +25,41 @@ def _run(cmd, env=None):
 
 
 def test_bench_contract_and_two_rank_rehearsal():
-    one = _run([sys.executable, "bench.py", "--workload", "c4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    one = _run([sys.executable, "bench.py", "--workload", "c4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     for key in CONTRACT_KEYS:
         assert key in one, key
     assert one["n_gpus"] == 1 and one["unit"] == "Mpixels/s" and one["dtype"] == "f32" and one["vs_baseline"] is None
     assert one["roofline"]["bound"] == "hbm" and 0 < one["roofline"]["frac"] < 1
     # `python bench.py --gpus 2` with no launcher around it: bench.py starts its own ranks (self_launch) and relays the line
     two = _run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1",
-                "--no-cpu-baseline"])
+                "--full", "--no-cpu-baseline"])
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and two["config"]["parallelism"] == "rowtile2+gather"
     assert two["image_checksum"] == one["image_checksum"]
     assert abs(two["config"]["geometry_fraction"] - one["config"]["geometry_fraction"]) < 1e-12
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries nothing that needs work beyond the timed steps; --dump-outputs writes the colour and both
+    LUTs of the last timed step as float32, within 64 MB, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    lines, dirs = [], [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        lines.append(_run([sys.executable, "bench.py", "--workload", "c2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(1920 * 1080 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-6)
+    for key in ("image_checksum", "cpu_baseline", "steady_state_cached_luts", "parity_vs_spirv_vectors", "literal_build"):
+        assert key not in line, key
+    names = ["color.npy", "skyview_lut.npy", "transmittance_lut.npy"]
+    assert sorted(p.name for p in dirs[0].iterdir()) == names
+    assert sum(p.stat().st_size for p in dirs[0].iterdir()) <= 64e6
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype == np.float32 and np.array_equal(a, b, equal_nan=True), name
+    color = np.load(dirs[0] / "color.npy")
+    assert color.shape == (1 << 20, 4) and 0.0 <= color.min() and 0.0 < color.max() <= 1.0
+    assert np.load(dirs[0] / "skyview_lut.npy").shape == (1024, 2048, 4)
 
 
 def test_bench_under_an_external_launcher_and_forced_tiling_on_rccl():
@@ -43,10 +67,10 @@ def test_bench_under_an_external_launcher_and_forced_tiling_on_rccl():
     with both collectives on RCCL in a world of one."""
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", "29655", "bench.py", "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "1", "--warmup", "1",
-                "--no-cpu-baseline"])
+                "--full", "--no-cpu-baseline"])
     assert two["n_gpus"] == 2 and two["config"]["collectives"] == "gloo"
     one = _run([sys.executable, "bench.py", "--gpus", "1", "--workload", "c4", "--force-tiled", "--steps", "2", "--warmup", "1",
-                "--no-cpu-baseline"])
+                "--full", "--no-cpu-baseline"])
     assert one["config"]["collectives"] == "nccl" and one["config"]["parallelism"] == "rowtile1+gather"
     assert one["image_checksum"] == two["image_checksum"]
 
@@ -58,7 +82,7 @@ def _single_gpu_c4_checksum():
     """The untiled 8K frame rendered by this build in this run (a committed checksum goes stale with every change of the
     arithmetic, e.g. round 3's contraction rule)."""
     if "checksum" not in _C4:
-        _C4["checksum"] = _run([sys.executable, "bench.py", "--workload", "c4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+        _C4["checksum"] = _run([sys.executable, "bench.py", "--workload", "c4", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
                                 "--no-extras"])["image_checksum"]
     return _C4["checksum"]
 
@@ -76,7 +100,7 @@ def test_n_rank_frame_through_the_c_abi_collectives_on_one_gpu(ranks, no_gather)
     if no_gather:  # szg_rowtile_gather's grouped ncclSend / ncclRecv form (what a library without ncclGather gets)
         env["SZG_RCCL_NO_GATHER"] = "1"
     many = _run([sys.executable, "bench.py", "--gpus", str(ranks), "--backend", "nccl", "--same-device", "--steps", "2", "--warmup", "1",
-                 "--no-cpu-baseline"], env=env)
+                 "--full", "--no-cpu-baseline"], env=env)
     cfg = many["config"]
     assert many["n_gpus"] == ranks and cfg["parallelism"] == f"rowtile{ranks}+gather" and cfg["collectives"] == "nccl"
     assert cfg["collective_api"].startswith("szg_rowtile_comm") and cfg["rccl_ranks"] == ranks
@@ -88,9 +112,9 @@ def test_replicas_line_of_the_batch_workload_through_the_self_launcher():
     path): bench.py starts its own ranks, every rank renders the same view, the line reports N x the pixels over the slowest
     rank's time with "replicas N" / weak scaling. Two ranks share the one GPU of the box here (--same-device), so the value
     says nothing; what is checked is the launch path, the aggregation and that no collective API is involved."""
-    one = _run([sys.executable, "bench.py", "--workload", "c5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+    one = _run([sys.executable, "bench.py", "--workload", "c5", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"])
     two = _run([sys.executable, "bench.py", "--gpus", "2", "--workload", "c5", "--backend", "gloo", "--same-device", "--steps", "2",
-                "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+                "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"])
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["config"]["parallelism"] == "replicas2"
     assert two["config"]["collectives"] is None and two["config"]["rccl_ranks"] is None
     assert two["image_checksum"] == one["image_checksum"]

@@ -79,7 +79,7 @@ def run(outdir, masks):
         rec = {"mask": m, "pin": json.loads(pin.stdout.strip().split("\n")[-1])}
         for wl in os.environ.get("SZG_CC_WORKLOADS", "c3,c2").split(","):
             b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", "30", "--warmup", "5",
-                                "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                                "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
             if b.returncode != 0:
                 print(f"mask {m:#x}: bench {wl} failed: {b.stderr[-500:]}", flush=True)
                 continue
