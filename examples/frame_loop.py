@@ -6,9 +6,10 @@
     staged buffers (cameras, atmospheres, directional lights)       renderer.cpp:302-342
     DeferredShadingPipeline::recordDrawCommands(meshes)             shadow raster, G-buffer raster, lights
     SkyViewComputePipeline::recordDrawCommands                      transmittance LUT, sky-view LUT, composite
+    --debug-lines: a box per instance + the shadow bounds, in green renderer.cpp:355-365, :417-427, :445-476
     OETF on the presented image                                     editor.cpp:303-340
 
-    python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm
+    python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm [--debug-lines [--line-width 2]]
 
 Needs an MI355X (no CPU fallback). Everything on the GPU is enqueued on one stream; the host only ticks the scene.
 """
@@ -32,6 +33,8 @@ def main():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--shadow-map", type=int, default=2048)
     ap.add_argument("--out", default="", help="write the last frame as a binary PPM (8 bit)")
+    ap.add_argument("--debug-lines", action="store_true", help="the editor's Debug Lines switch (engineui.cpp:95-109)")
+    ap.add_argument("--line-width", type=float, default=1.0)
     args = ap.parse_args()
 
     import torch
@@ -79,6 +82,8 @@ def main():
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=len(spots), max_shadow_maps=2 + len(spots), shadow_map_dim=args.shadow_map)
     sky = pl.SkyViewComputePipeline.create()
     rect = pl.rect(W, H)
+    debug_lines = pl.DebugLines()  # Renderer::m_debugLines, DEBUGLINES_CAPACITY vertices (renderer.hpp:103)
+    debug_lines.enabled, debug_lines.lineWidth = args.debug_lines, args.line_width
 
     t_start = time.perf_counter()
     elapsed, dt = 0.0, 1.0 / 60.0
@@ -86,12 +91,15 @@ def main():
         # Scene::tick
         lib().szg_scene_tick_sun(C.byref(sun_animation), C.byref(atmosphere), dt * 50.0)  # 100x speed (scene.cpp:89): a slow sunset over a few hundred frames
         scene_meshes, casters = [], []
+        debug_lines.clear()  # renderer.cpp:287
         for inst in instances:
             lib().szg_tick_mesh_instance(inst["animation"], inst["originals"], inst["transforms"], inst["n"], elapsed, dt, inst["models"],
                                          inst["mits"])
             scene_meshes.append(meshes.MeshInstanced(inst["vertices"], inst["indices"], [(0, len(inst["indices"]), material)],
                                                      list(inst["models"])))
             casters.append(abi.ShadowCaster(inst["bounds"], inst["transforms"], inst["n"], 1, 1, 0))
+            for t in inst["transforms"]:
+                debug_lines.pushBox(t, inst["bounds"])  # renderer.cpp:355-365
         bounds = abi.AABB()
         lib().szg_calculate_shadow_bounds((abi.ShadowCaster * len(casters))(*casters), len(casters), C.byref(bounds))
         atm, sun, moon = scene.atmosphere_baked(atmosphere, bounds)
@@ -103,6 +111,8 @@ def main():
             buf.recordCopyToDevice()
         deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
         sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
+        debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423
+        debug_lines.recordDraw(None, 0, target, rect, cameras)  # renderer.cpp:425-427, :445-476 (only when enabled)
         pl.recordOETF(None, target, W, H)
         elapsed += dt
     torch.cuda.synchronize()
@@ -115,6 +125,9 @@ def main():
             f.write(f"P6 {W} {H} 255\n".encode())
             f.write((image[..., :3] >> 8).astype(np.uint8).tobytes())
         print("wrote", args.out)
+    if args.debug_lines:
+        print(f"debug lines: {debug_lines.lastFrameDrawResults.verticesDrawn // 2} lines, width {debug_lines.lineWidth}")
+    debug_lines.cleanup()
     deferred.cleanup()
     sky.destroy()
     return image

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SZG_ABI_VERSION 1
+#define SZG_ABI_VERSION 2
 
 /* ------------------------------------------------------------------------- */
 /* Status codes (reference: construction returns optional/nullptr + log,      */

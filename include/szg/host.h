@@ -14,6 +14,7 @@
 #define SZG_HOST_H
 
 #include "szg/abi.h"
+#include "szg/raster.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -163,6 +164,24 @@ void szg_make_spot(const szg_spotlight_params* params, szg_spot_light_packed* ou
 /* scene.cpp:218-229 addSpotlight defaults (strength 1000, falloff 1/1, fov 30, near .1, far 1000) */
 void szg_spotlight_params_default(const float color_rgb[3], const float position[3], const float eulers[3],
                                   szg_spotlight_params* out);
+/* DebugLines list builders (renderer/pipelines/debuglines.cpp:23-124), one per DebugLines::push*. Each writes its segments
+ * as szg_vertex_packed pairs into `out`: start vertex uv_x 0, colour red (1, 0, 0, 1); end vertex uv_x 1, colour blue
+ * (0, 0, 1, 1); normal and uv_y 0. Quaternions are {x, y, z, w} (glm's default storage); quat * vec3 restates glm's
+ * v + ((uv * q.w) + uuv) * 2 with uv = cross(q.xyz, v), uuv = cross(q.xyz, uv). The restatements are checked against
+ * numpy restatements of the same formulas (tests/test_debuglines_host.py), not against glm itself. */
+/* debuglines.cpp:23-46 push(start, end): 2 vertices */
+void szg_debug_lines_segment(const float start[3], const float end[3], szg_vertex_packed out[2]);
+/* debuglines.cpp:50-58 pushQuad(a, b, c, d): segments ab, bc, cd, da, 8 vertices */
+void szg_debug_lines_quad(const float a[3], const float b[3], const float c[3], const float d[3], szg_vertex_packed out[8]);
+/* debuglines.cpp:60-70 pushRectangleAxes: the quad c+A+B, c+A-B, c-A-B, c-A+B, 8 vertices */
+void szg_debug_lines_rectangle_axes(const float center[3], const float extent_a[3], const float extent_b[3], szg_vertex_packed out[8]);
+/* debuglines.cpp:72-82 pushRectangleOriented(center, quat, extents2), 8 vertices */
+void szg_debug_lines_rectangle_oriented(const float center[3], const float quat[4], const float extents[2], szg_vertex_packed out[8]);
+/* debuglines.cpp:84-99 pushBox(center, quat, extents): 6 rectangles, 48 vertices */
+void szg_debug_lines_box(const float center[3], const float quat[4], const float extents[3], szg_vertex_packed out[48]);
+/* debuglines.cpp:101-124 pushBox(Transform, AABB): axes and centre through Transform::toMatrix (szg_transform_matrix) and
+ * glm's mat4 * vec4, 48 vertices */
+void szg_debug_lines_box_transform(const szg_transform* parent, const szg_aabb* box, szg_vertex_packed out[48]);
 /* scene.cpp:532-574: advance the sun animation by dt seconds and set sunEulerAngles.x */
 void szg_scene_tick_sun(szg_sun_animation* anim, szg_atmosphere* atmosphere, double delta_time_seconds);
 

@@ -12,6 +12,7 @@
 //   GBuffer / ShadowPassArray   gbuffer.hpp, shadowpass.hpp szg_gbuffer / szg_shadowmaps
 //   DeferredShadingPipeline     pipelines/deferred.hpp:23  szg::DeferredShadingPipeline
 //   SkyViewComputePipeline      pipelines/skyview.hpp:24   szg::SkyViewComputePipeline
+//   DebugLineGraphicsPipeline   pipelines.hpp:238-268      szg::DebugLineGraphicsPipeline (szg/debuglines.h)
 //   std::span<MeshInstanced const> sceneGeometry           szg_fill_scene const* (synthetic)
 //
 // Error behaviour follows the reference: construction failures give an invalid object /
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/debuglines.h"
 #include "szg/raster.h"
 #include "szg/host.h"
 
@@ -409,6 +411,62 @@ struct SkyViewComputePipeline
 private:
     explicit SkyViewComputePipeline(szg_skyview_t* h) : m_handle(h) {}
     szg_skyview_t* m_handle{nullptr};
+    int m_lastStatus{SZG_OK};
+};
+
+// pipelines.hpp:39-44
+struct DrawResultsGraphics
+{
+    size_t drawCalls{0};
+    size_t verticesDrawn{0};
+    size_t indicesDrawn{0};
+};
+
+// pipelines.hpp:238-268 over szg/debuglines.h: the debug-line pass. Without the Vulkan handles: no image formats, no depth
+// attachment (compare ALWAYS into a renderer-private image nothing reads, szg/debuglines.h), no index buffer (the
+// reference binds it and draws non-indexed).
+struct DebugLineGraphicsPipeline
+{
+    using VertexPacked = szg_vertex_packed;
+
+    explicit DebugLineGraphicsPipeline(uint32_t vertexCapacity = SZG_DEBUG_LINES_CAPACITY, int device = 0)
+    {
+        if (szg_debug_lines_create(&m_handle, vertexCapacity, device) != SZG_OK)
+        {
+            std::fprintf(stderr, "[szg] DebugLineGraphicsPipeline: %s\n", szg_last_error());
+            m_handle = nullptr;
+        }
+    }
+    ~DebugLineGraphicsPipeline() { cleanup(); }
+    DebugLineGraphicsPipeline(DebugLineGraphicsPipeline const&) = delete;
+    auto operator=(DebugLineGraphicsPipeline const&) -> DebugLineGraphicsPipeline& = delete;
+
+    [[nodiscard]] auto valid() const -> bool { return m_handle != nullptr; }
+    [[nodiscard]] auto lastStatus() const -> int { return m_lastStatus; }
+
+    // pipelines.cpp:463-581: endpoints.deviceSize() vertices as a line list over the scene colour
+    auto recordDrawCommands(hipStream_t cmd, float lineWidth, szg_rect drawRect, SceneTexture& sceneTexture, uint32_t cameraIndex,
+                            TStagedBuffer<CameraPacked> const& cameras, TStagedBuffer<VertexPacked> const& endpoints,
+                            szg_rowtile const* tile = nullptr) -> DrawResultsGraphics
+    {
+        uint32_t const n = static_cast<uint32_t>(endpoints.deviceSize());
+        if (detail::note(szg_debug_lines_record(m_handle, cmd, lineWidth, drawRect, tile, &sceneTexture.texture(), cameraIndex,
+                                                cameras.deviceAddress(), endpoints.deviceAddress(), n),
+                         "szg_debug_lines_record", m_lastStatus) != SZG_OK)
+        {
+            return DrawResultsGraphics{};
+        }
+        return DrawResultsGraphics{1, n, n};
+    }
+
+    void cleanup()
+    {
+        szg_debug_lines_destroy(m_handle);
+        m_handle = nullptr;
+    }
+
+  private:
+    szg_debug_lines_t* m_handle{nullptr};
     int m_lastStatus{SZG_OK};
 };
 } // namespace szg

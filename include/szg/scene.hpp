@@ -8,8 +8,9 @@
 //   Scene                 renderer/scene.hpp:160-222        szg::Scene: sunAnimation, atmosphere, camera, spotlights(+Render),
 //                         renderer/scene.cpp:95-574         calculateShadowBounds, shadowBounds, geometry, addMeshInstance,
 //                                                           addSpotlight, defaultScene, tick
-//   Renderer::recordDraw  renderer/renderer.cpp:278-443     szg::Renderer::recordDraw (deferred pipeline branch; the debug
-//                                                           lines and the generic compute collection are editor features)
+//   DebugLines            pipelines/debuglines.hpp:22-68    szg::DebugLines: enabled, lineWidth, vertices, push* builders
+//   Renderer::recordDraw  renderer/renderer.cpp:278-476     szg::Renderer::recordDraw (deferred pipeline branch, debug lines
+//                                                           included; the generic compute collection is an editor demo)
 //
 // Not mirrored: Scene::handleInput (window input), Scene::diagonalWaveScene (its instance rotations come from the
 // reference's random quaternion source and are not reproducible).
@@ -167,6 +168,69 @@ struct Scene
     std::vector<MeshInstanced> m_geometry{};
 };
 
+// pipelines/debuglines.hpp:22-68: the editor's "Debug Lines" overlay (engineui.cpp:95-109). The list is a staged buffer of
+// SZG_DEBUG_LINES_CAPACITY vertices (renderer.hpp:103); the push* methods are the C builders of szg/host.h. Pushing past the
+// capacity drops the push with a log line, as TStagedBuffer::push does. No index buffer: the reference draws non-indexed.
+struct DebugLines
+{
+    using VertexPacked = szg_vertex_packed;
+
+    TStagedBuffer<VertexPacked> vertices{};
+    std::unique_ptr<DebugLineGraphicsPipeline> pipeline{};
+    DrawResultsGraphics lastFrameDrawResults{};
+    bool enabled{false};
+    float lineWidth{SZG_DEBUG_LINES_DEFAULT_WIDTH};
+
+    static auto create(uint32_t capacity = SZG_DEBUG_LINES_CAPACITY) -> DebugLines
+    {
+        DebugLines d{};
+        d.vertices = TStagedBuffer<VertexPacked>::allocate(capacity);
+        d.pipeline = std::make_unique<DebugLineGraphicsPipeline>(capacity);
+        return d;
+    }
+    [[nodiscard]] auto valid() const -> bool { return vertices.valid() && pipeline != nullptr && pipeline->valid(); }
+
+    void clear() { vertices.clearStaged(); }
+    void push(const float start[3], const float end[3])
+    {
+        VertexPacked out[2];
+        szg_debug_lines_segment(start, end, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    void pushQuad(const float a[3], const float b[3], const float c[3], const float d[3])
+    {
+        VertexPacked out[8];
+        szg_debug_lines_quad(a, b, c, d, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    void pushRectangleAxes(const float center[3], const float extentA[3], const float extentB[3])
+    {
+        VertexPacked out[8];
+        szg_debug_lines_rectangle_axes(center, extentA, extentB, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    // orientation: quaternion {x, y, z, w}
+    void pushRectangleOriented(const float center[3], const float orientation[4], const float extents[2])
+    {
+        VertexPacked out[8];
+        szg_debug_lines_rectangle_oriented(center, orientation, extents, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    void pushBox(const float center[3], const float orientation[4], const float extents[3])
+    {
+        VertexPacked out[48];
+        szg_debug_lines_box(center, orientation, extents, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    void pushBox(szg_transform const& parent, szg_aabb const& box)
+    {
+        VertexPacked out[48];
+        szg_debug_lines_box_transform(&parent, &box, out);
+        vertices.push(std::span<VertexPacked const>{out});
+    }
+    void recordCopy(hipStream_t cmd) { vertices.recordCopyToDevice(cmd); }
+};
+
 // The part of Renderer (renderer.hpp / renderer.cpp:114-124, :278-443) that owns the staged parameter buffers and the two
 // pipelines and records one frame of the deferred + atmosphere path.
 struct Renderer
@@ -179,8 +243,9 @@ struct Renderer
         r.m_directionalLightsBuffer = TStagedBuffer<DirectionalLightPacked>::allocate(2);
         r.m_deferredShadingPipeline = std::make_unique<DeferredShadingPipeline>(capacityWidth, capacityHeight, 16, 10, shadowMapDimension);
         r.m_skyViewComputePipeline = SkyViewComputePipeline::create();
+        r.m_debugLines = DebugLines::create(); // renderer.cpp:114-124, DEBUGLINES_CAPACITY (renderer.hpp:103)
         if (!r.m_camerasBuffer.valid() || !r.m_atmospheresBuffer.valid() || !r.m_directionalLightsBuffer.valid() ||
-            !r.m_deferredShadingPipeline->valid() || r.m_skyViewComputePipeline == nullptr)
+            !r.m_deferredShadingPipeline->valid() || r.m_skyViewComputePipeline == nullptr || !r.m_debugLines.valid())
         {
             return std::nullopt;
         }
@@ -213,11 +278,19 @@ struct Renderer
         m_directionalLightsBuffer.push(lights);
         m_directionalLightsBuffer.recordCopyToDevice(cmd);
 
+        m_debugLines.clear(); // renderer.cpp:287
         std::vector<szg_mesh_instanced> geometry;
         for (MeshInstanced const& instance : scene.geometry())
         {
             instance.recordCopyToDevice(cmd); // renderer.cpp:344-353
             geometry.push_back(instance.view());
+            if (auto const mesh = instance.getMesh(); mesh != nullptr)
+            {
+                for (szg_transform const& transform : instance.transforms) // renderer.cpp:355-365
+                {
+                    m_debugLines.pushBox(transform, mesh->vertexBounds);
+                }
+            }
         }
         std::vector<SpotLightPacked> const none{};
         m_deferredShadingPipeline->recordDrawCommands(cmd, sceneSubregion, sceneTexture, m_renderAtmosphere ? 1u : 0u,
@@ -229,9 +302,27 @@ struct Renderer
                                                          m_deferredShadingPipeline->shadowMaps(), 0, m_atmospheresBuffer, 0,
                                                          m_camerasBuffer, 0, m_directionalLightsBuffer);
         }
+        float const identity[4] = {0.0f, 0.0f, 0.0f, 1.0f}; // glm::identity<glm::quat>()
+        m_debugLines.pushBox(bounds.center, identity, bounds.half_extent); // renderer.cpp:417-423
+        recordDrawDebugLines(cmd, 0, sceneTexture, sceneSubregion, m_camerasBuffer); // renderer.cpp:425-427
+    }
+
+    // renderer.cpp:445-476: only when enabled and the list is not empty (so with the default enabled = false the frame
+    // launches exactly what it launched without the pass)
+    void recordDrawDebugLines(hipStream_t cmd, uint32_t cameraIndex, SceneTexture& sceneTexture, szg_rect sceneSubregion,
+                              TStagedBuffer<CameraPacked> const& camerasBuffer)
+    {
+        m_debugLines.lastFrameDrawResults = {};
+        if (m_debugLines.enabled && m_debugLines.vertices.stagedSize() > 0)
+        {
+            m_debugLines.recordCopy(cmd);
+            m_debugLines.lastFrameDrawResults = m_debugLines.pipeline->recordDrawCommands(
+                cmd, m_debugLines.lineWidth, sceneSubregion, sceneTexture, cameraIndex, camerasBuffer, m_debugLines.vertices);
+        }
     }
 
     [[nodiscard]] auto deferredShadingPipeline() -> DeferredShadingPipeline& { return *m_deferredShadingPipeline; }
+    [[nodiscard]] auto debugLines() -> DebugLines& { return m_debugLines; }
 
   private:
     bool m_renderAtmosphere{true};
@@ -240,5 +331,6 @@ struct Renderer
     TStagedBuffer<DirectionalLightPacked> m_directionalLightsBuffer{};
     std::unique_ptr<DeferredShadingPipeline> m_deferredShadingPipeline{};
     std::unique_ptr<SkyViewComputePipeline> m_skyViewComputePipeline{};
+    DebugLines m_debugLines{};
 };
 } // namespace szg

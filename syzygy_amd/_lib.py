@@ -37,12 +37,18 @@ def lib():
         import torch  # noqa: F401
 
         handle = ctypes.CDLL(path)
+        # the version first: a library of another ABI version lacks or mis-declares symbols, and binding it would fail
+        # with an AttributeError that hides the real cause
+        handle.szg_abi_version.restype = ctypes.c_int
+        handle.szg_abi_version.argtypes = []
+        version = handle.szg_abi_version()
+        if version != abi.SZG_ABI_VERSION:
+            raise RuntimeError(f"{path}: ABI version {version}, this package needs {abi.SZG_ABI_VERSION}; rebuild the library")
         abi.bind(handle, abi.ABI_FUNCTIONS)
         abi.bind(handle, abi.HOST_FUNCTIONS)
         abi.bind(handle, abi.RASTER_FUNCTIONS)
         abi.bind(handle, abi.ASSET_FUNCTIONS)
-        if handle.szg_abi_version() != abi.SZG_ABI_VERSION:
-            raise RuntimeError("libszg_hip.so ABI version mismatch")
+        abi.bind(handle, abi.DEBUGLINE_FUNCTIONS)
         _LIB = handle
     return _LIB
 

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-SZG_ABI_VERSION = 1
+SZG_ABI_VERSION = 2
 
 SZG_OK = 0
 SZG_ERR_INVALID_ARGUMENT = -1
@@ -507,6 +507,25 @@ HOST_FUNCTIONS = {
     "szg_make_spot": (None, [P(SpotlightParams), P(SpotLightPacked)]),
     "szg_spotlight_params_default": (None, [P(C.c_float), P(C.c_float), P(C.c_float), P(SpotlightParams)]),
     "szg_scene_tick_sun": (None, [P(SunAnimation), P(Atmosphere), C.c_double]),
+    "szg_debug_lines_segment": (None, [P(C.c_float), P(C.c_float), P(VertexPacked)]),
+    "szg_debug_lines_quad": (None, [P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(VertexPacked)]),
+    "szg_debug_lines_rectangle_axes": (None, [P(C.c_float), P(C.c_float), P(C.c_float), P(VertexPacked)]),
+    "szg_debug_lines_rectangle_oriented": (None, [P(C.c_float), P(C.c_float), P(C.c_float), P(VertexPacked)]),
+    "szg_debug_lines_box": (None, [P(C.c_float), P(C.c_float), P(C.c_float), P(VertexPacked)]),
+    "szg_debug_lines_box_transform": (None, [P(Transform), P(AABB), P(VertexPacked)]),
+}
+
+# include/szg/debuglines.h
+SZG_DEBUG_LINES_CAPACITY = 1000
+SZG_DEBUG_LINES_DEFAULT_WIDTH = 1.0
+SZG_DEBUG_LINES_MAX_WIDTH = 256.0
+SZG_DEBUG_LINES_GUARD_BAND = 16777216.0
+SZG_DEBUG_LINES_MAX_CAPACITY = 1 << 24
+
+DEBUGLINE_FUNCTIONS = {
+    "szg_debug_lines_create": (C.c_int, [P(VP), U32, C.c_int]),
+    "szg_debug_lines_destroy": (None, [VP]),
+    "szg_debug_lines_record": (C.c_int, [VP, VP, C.c_float, Rect, P(RowTile), P(SceneTexture), U32, VP, VP, U32]),
 }
 
 

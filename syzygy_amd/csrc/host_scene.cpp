@@ -674,3 +674,88 @@ void szg_scene_tick_sun(szg_sun_animation* anim, szg_atmosphere* atmosphere, dou
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------
+// DebugLines builders, renderer/pipelines/debuglines.cpp:23-124
+namespace
+{
+inline V3 cross(V3 x, V3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; } // glm::cross
+inline V3 mulc(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }                                    // vec3 * vec3
+// glm qua * vec3: v + ((uv * q.w) + uuv) * 2
+V3 rotate(const float q[4], V3 v)
+{
+    V3 const qv{q[0], q[1], q[2]};
+    V3 const uv = cross(qv, v);
+    V3 const uuv = cross(qv, uv);
+    return v + ((uv * q[3]) + uuv) * 2.0f;
+}
+void segment(V3 start, V3 end, szg_vertex_packed* out)
+{
+    std::memset(out, 0, 2 * sizeof *out);
+    store(out[0].position, start);
+    out[0].uv_x = 0.0f;
+    out[0].color[0] = 1.0f;
+    out[0].color[3] = 1.0f;
+    store(out[1].position, end);
+    out[1].uv_x = 1.0f;
+    out[1].color[2] = 1.0f;
+    out[1].color[3] = 1.0f;
+}
+void quad(V3 a, V3 b, V3 c, V3 d, szg_vertex_packed* out)
+{
+    segment(a, b, out);
+    segment(b, c, out + 2);
+    segment(c, d, out + 4);
+    segment(d, a, out + 6);
+}
+void rectangleAxes(V3 center, V3 A, V3 B, szg_vertex_packed* out)
+{
+    quad(center + A + B, center + A - B, center - A - B, center - A + B, out);
+}
+void box(V3 center, V3 right, V3 forward, V3 up, szg_vertex_packed* out)
+{
+    rectangleAxes(center - up, right, forward, out);
+    rectangleAxes(center + up, right, forward, out + 8);
+    rectangleAxes(center - right, forward, up, out + 16);
+    rectangleAxes(center + right, forward, up, out + 24);
+    rectangleAxes(center - forward, up, right, out + 32);
+    rectangleAxes(center + forward, up, right, out + 40);
+}
+V3 xyz(V4 v) { return {v.x, v.y, v.z}; }
+} // namespace
+
+extern "C" {
+void szg_debug_lines_segment(const float start[3], const float end[3], szg_vertex_packed out[2]) { segment(v3(start), v3(end), out); }
+void szg_debug_lines_quad(const float a[3], const float b[3], const float c[3], const float d[3], szg_vertex_packed out[8])
+{
+    quad(v3(a), v3(b), v3(c), v3(d), out);
+}
+void szg_debug_lines_rectangle_axes(const float center[3], const float extent_a[3], const float extent_b[3], szg_vertex_packed out[8])
+{
+    rectangleAxes(v3(center), v3(extent_a), v3(extent_b), out);
+}
+void szg_debug_lines_rectangle_oriented(const float center[3], const float quat[4], const float extents[2], szg_vertex_packed out[8])
+{
+    V3 const scale{extents[0], 1.0f, extents[1]};
+    V3 const right = rotate(quat, mulc(scale, WORLD_RIGHT));
+    V3 const forward = rotate(quat, mulc(scale, WORLD_FORWARD));
+    rectangleAxes(v3(center), right, forward, out);
+}
+void szg_debug_lines_box(const float center[3], const float quat[4], const float extents[3], szg_vertex_packed out[48])
+{
+    V3 const e = v3(extents);
+    box(v3(center), rotate(quat, mulc(e, WORLD_RIGHT)), rotate(quat, mulc(e, WORLD_FORWARD)), rotate(quat, mulc(e, WORLD_UP)), out);
+}
+void szg_debug_lines_box_transform(const szg_transform* parent, const szg_aabb* bounds, szg_vertex_packed out[48])
+{
+    szg_mat4 m;
+    szg_transform_matrix(parent->translation, parent->eulerAnglesRadians, parent->scale, &m);
+    V3 const h = v3(bounds->half_extent);
+    V3 const r = mulc(h, WORLD_RIGHT), f = mulc(h, WORLD_FORWARD), u = mulc(h, WORLD_UP);
+    V3 const right = xyz(mul(m, V4{r.x, r.y, r.z, 0.0f}));
+    V3 const forward = xyz(mul(m, V4{f.x, f.y, f.z, 0.0f}));
+    V3 const up = xyz(mul(m, V4{u.x, u.y, u.z, 0.0f}));
+    V3 const center = xyz(mul(m, V4{bounds->center[0], bounds->center[1], bounds->center[2], 1.0f}));
+    box(center, right, forward, up, out);
+}
+} // extern "C"

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "szg/abi.h"
+#include "szg/debuglines.h"
 #include "szg/raster.h"
 
 namespace szg
@@ -187,4 +188,30 @@ hipError_t launch_oetf_table(hipStream_t s, unsigned short* table, unsigned func
 hipError_t launch_oetf(hipStream_t s, const szg_image& image, unsigned width, unsigned height, const unsigned short* table);
 hipError_t launch_compose_rowtiles(hipStream_t s, const void* gathered, size_t tileStrideBytes, unsigned nranks,
                                    unsigned blockRows, const szg_image& dst, unsigned width, unsigned height);
+
+// ---- debug-line pass (kernels_debuglines.hip, include/szg/debuglines.h) ----
+// One line after setup: viewport endpoints, the coverage terms of the header, and its major-axis pixel range.
+struct DebugLineRec
+{
+    float xa, ya, xb, yb;
+    float dx, dy, L2, w2; // coverage terms (w2 = line_width * line_width)
+    float half;           // minor-axis candidate half-width around the centre line (pixels)
+    float slope;          // d_minor / d_major
+    int first;            // first major-axis pixel of the clamped range
+    unsigned major;       // 0: x-major, 1: y-major
+};
+static_assert(sizeof(DebugLineRec) == 48, "DebugLineRec layout");
+// Device scratch of one pipeline object, sized at creation from its vertex capacity (szg_api.cpp).
+struct DebugLineBuffers
+{
+    DebugLineRec* recs = nullptr;          // [lines]
+    unsigned long long* steps = nullptr;   // [lines + 1] step counts, last = 0
+    unsigned long long* offsets = nullptr; // [lines + 1] exclusive scan; offsets[lines] = total
+    void* scanTemp = nullptr;
+    size_t scanTempBytes = 0;
+};
+hipError_t debug_lines_scan_temp_bytes(unsigned lineCapacity, size_t& bytes);
+hipError_t launch_debug_lines(hipStream_t s, const szg_scene_texture& scene, unsigned W, unsigned H, TileArgs tile,
+                              const szg_camera_packed* d_cam, unsigned camIndex, const szg_vertex_packed* d_vertices,
+                              unsigned lineCount, float lineWidth, DebugLineBuffers& b);
 } // namespace szg

@@ -6,10 +6,13 @@ Names, argument order and meaning follow the reference:
   SceneTexture              renderer/scenetexture.hpp:11-81
   DeferredShadingPipeline   renderer/pipelines/deferred.hpp:23-119
   SkyViewComputePipeline    renderer/pipelines/skyview.hpp:24-51
+  DebugLines                renderer/pipelines/debuglines.hpp:22-68
+  DebugLineGraphicsPipeline renderer/pipelines.hpp:238-268
 with `cmd` (VkCommandBuffer) replaced by a HIP stream handle and Vulkan images by
 linear device buffers. torch is used only to own device memory and streams.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -464,3 +467,110 @@ class SkyViewComputePipeline:
             self.destroy()
         except Exception:
             pass
+
+
+# pipelines.hpp:39-44
+DrawResultsGraphics = namedtuple("DrawResultsGraphics", ["drawCalls", "verticesDrawn", "indicesDrawn"])
+
+
+def _f(values, n):
+    values = [float(v) for v in values]
+    assert len(values) == n, values
+    return (C.c_float * n)(*values)
+
+
+class DebugLineGraphicsPipeline:
+    """pipelines.hpp:238-268 over include/szg/debuglines.h: the debug-line pass as a HIP line rasteriser. The depth
+    attachment of the reference is dropped (compare ALWAYS, a renderer-private image nothing reads)."""
+
+    def __init__(self, vertexCapacity=abi.SZG_DEBUG_LINES_CAPACITY, device_index=0):
+        handle = C.c_void_p()
+        check(lib().szg_debug_lines_create(C.byref(handle), int(vertexCapacity), int(device_index)))
+        self._h = handle
+        self.vertexCapacity = int(vertexCapacity)
+
+    def recordDrawCommands(self, cmd, lineWidth, drawRect, sceneTexture, cameraIndex, cameras, endpoints, tile=None):
+        """pipelines.cpp:463-581: draws endpoints.deviceSize() vertices as a line list over the scene colour."""
+        st = sceneTexture.abi()
+        n = int(endpoints.deviceSize())
+        check(lib().szg_debug_lines_record(
+            self._h, _stream_handle(cmd), C.c_float(lineWidth), drawRect, C.byref(tile) if tile is not None else None,
+            C.byref(st), int(cameraIndex), C.c_void_p(cameras.deviceAddress()), C.c_void_p(endpoints.deviceAddress()), n))
+        return DrawResultsGraphics(1, n, n)
+
+    def cleanup(self):
+        if self._h:
+            lib().szg_debug_lines_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.cleanup()
+        except Exception:
+            pass
+
+
+class DebugLines:
+    """debuglines.hpp:22-68: the line list (a TStagedBuffer of VertexPacked, renderer.hpp:103 capacity), the switch and the
+    width; the push* builders are the C restatements of debuglines.cpp:23-124 (szg/host.h). Pushing past the capacity
+    raises, as TStagedBuffer.push does."""
+
+    def __init__(self, capacity=abi.SZG_DEBUG_LINES_CAPACITY, device="cuda:0", device_index=0):
+        self.vertices = TStagedBuffer(abi.VertexPacked, capacity, device)
+        self.pipeline = DebugLineGraphicsPipeline(capacity, device_index)
+        self.lastFrameDrawResults = DrawResultsGraphics(0, 0, 0)
+        self.enabled = False
+        self.lineWidth = abi.SZG_DEBUG_LINES_DEFAULT_WIDTH
+
+    def clear(self):
+        self.vertices.clearStaged()
+
+    def _push(self, out):
+        self.vertices.push(list(out))
+
+    def push(self, start, end):
+        out = (abi.VertexPacked * 2)()
+        lib().szg_debug_lines_segment(_f(start, 3), _f(end, 3), out)
+        self._push(out)
+
+    def pushQuad(self, a, b, c, d):
+        out = (abi.VertexPacked * 8)()
+        lib().szg_debug_lines_quad(_f(a, 3), _f(b, 3), _f(c, 3), _f(d, 3), out)
+        self._push(out)
+
+    def pushRectangleAxes(self, center, extentA, extentB):
+        out = (abi.VertexPacked * 8)()
+        lib().szg_debug_lines_rectangle_axes(_f(center, 3), _f(extentA, 3), _f(extentB, 3), out)
+        self._push(out)
+
+    def pushRectangleOriented(self, center, orientation, extents):
+        """`orientation` is a quaternion {x, y, z, w}."""
+        out = (abi.VertexPacked * 8)()
+        lib().szg_debug_lines_rectangle_oriented(_f(center, 3), _f(orientation, 4), _f(extents, 2), out)
+        self._push(out)
+
+    def pushBox(self, *args):
+        """pushBox(center, orientation {x, y, z, w}, extents) or pushBox(abi.Transform, abi.AABB)."""
+        out = (abi.VertexPacked * 48)()
+        if len(args) == 2:
+            parent, box = args
+            lib().szg_debug_lines_box_transform(C.byref(parent), C.byref(box), out)
+        else:
+            center, orientation, extents = args
+            lib().szg_debug_lines_box(_f(center, 3), _f(orientation, 4), _f(extents, 3), out)
+        self._push(out)
+
+    def recordCopy(self, cmd=None):
+        self.vertices.recordCopyToDevice(cmd)
+
+    def recordDraw(self, cmd, cameraIndex, sceneTexture, sceneSubregion, cameras, tile=None):
+        """Renderer::recordDrawDebugLines (renderer.cpp:445-476): copy and draw only when enabled and the list is not empty."""
+        self.lastFrameDrawResults = DrawResultsGraphics(0, 0, 0)
+        if self.enabled and self.vertices.stagedSize() > 0:
+            self.recordCopy(cmd)
+            self.lastFrameDrawResults = self.pipeline.recordDrawCommands(cmd, self.lineWidth, sceneSubregion, sceneTexture,
+                                                                         cameraIndex, cameras, self.vertices, tile)
+        return self.lastFrameDrawResults
+
+    def cleanup(self):
+        self.pipeline.cleanup()
