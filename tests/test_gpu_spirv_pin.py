@@ -46,9 +46,9 @@ def test_literal_kernels_reproduce_the_reference_spirv_bit_for_bit():
 def test_product_kernels_stay_within_1e4_and_one_unorm16_step_of_the_reference_spirv():
     """The product library on the same inputs. It fuses a * b + c only at the site classes of include/szg/contraction.h that
     were measured, alone and together, to leave EVERY recorded value within north_star's 1e-4 relative and one UNORM16 step
-    (profiles/r03_contraction_classes.md; round 2 fused everywhere and was 2.3e-3 / 7 steps away). Measured on MI355X for the
-    product's rule: camera.comp 6.6e-6 / 1 step, sky-view texels 2.2e-7, transmittance texels bit-identical, lights 2.9e-6.
-    The bounds are the bar itself, not a multiple of the measurement."""
+    (profiles/r03_contraction_classes.md; round 2 fused everywhere and was 2.3e-3 / 7 steps away). These vectors are a sample
+    (84 sky-view texels, none next to the horizon): tests/test_gpu_contraction_whole_images.py holds the rule to the same bar
+    on whole LUTs and frames. The bounds are the bar itself, not a multiple of the measurement."""
     out = _child(None)
     assert out["library"] == "libszg_hip.so"
     assert 0 < out["camera_mismatches"] + out["lights_mismatches"]  # the two builds are different programs

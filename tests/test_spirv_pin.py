@@ -217,7 +217,7 @@ def test_the_product_rule_stays_within_1e4_and_one_step_of_the_spirv_vectors(vec
 
 def test_the_product_rule_leaves_the_lut_shaders_at_the_literal_values(vec):
     """transmittance_LUT.comp: no fused class occurs in it, the default oracle IS the literal one there (whole LUT, SHA-256).
-    skyview_LUT.comp: within 1e-4 of the literal texels (measured 2.2e-7)."""
+    skyview_LUT.comp: within 1e-4 of the literal texels (whole LUTs: tests/test_contraction_whole_images.py)."""
     atm = _block(abi.AtmospherePacked, vec["atm_0"])
     t = ob.transmittance_lut(atm, 512, 128, threads=8)
     assert hashlib.sha256(t.tobytes()).digest() == bytes(vec["tlut_sha256_0"])
