@@ -13,8 +13,13 @@
  * manipulation — all correctly rounded and therefore identical on x86-64 and gfx950
  * (checked on hardware: DESIGN.md "numerics").
  *
- * Accuracy against float64 libm is measured in tests/test_fpmath.py:
- *   exp <= 1 ULP, log <= 3 ULP, sin/cos <= 1.6 ULP on |x| <= 10, asin/acos <= 2.5 ULP,
+ * Accuracy against float64, largest error over EVERY binary32 input of the range (ULP of the result's binade, 2^-126 floor;
+ * measured on the GPU by tests/test_gpu_device_arith.py, the worst inputs kept in tests/test_fpmath.py):
+ *   exp <= 0.99 ULP on [-104, 88.72] (denormal results in units of 2^-149; +inf where the result overflows),
+ *   log <= 2.85 ULP on (0, +inf], asin <= 2.36 ULP and acos <= 1.28 ULP on [-1, 1],
+ *   sin <= 1.42 ULP and cos <= 1.56 ULP on [-pi, pi] (absolute error < 1e-7 there), but sin/cos <= 5.8 ULP on
+ *   [-pi/2, 3pi/2] and [-10, 10]: next to their zeros (cos(0x1.2d97c8p+2), sin(-0x1.2d97c8p+3)) a relative bound is hardest
+ *   to meet; GLSL bounds only their absolute error (2^-11),
  *   pow = exp(y * log(x)) (error grows with |y log x| exactly as GLSL's definition).
  * Polynomial coefficients: exp/log after SLEEF 3 (Boost licence) single-precision
  * kernels; sin/cos/asin after Cephes single-precision kernels (S. Moshier).
@@ -34,17 +39,18 @@ SZG_FP_FN int szg_float_to_bits(float f) { return __builtin_bit_cast(int, f); }
 /* 2^k for k in [-126, 127] */
 SZG_FP_FN float szg_pow2i(int k) { return szg_bits_to_float((k + 127) << 23); }
 
-/* n / d for a denominator d in [1.75, 2.5] and |n| <= 0.5 (the only use: log's (m-1)/(m+1)).
- * Host: the IEEE operator. Device: the same correctly rounded quotient computed without hipcc's
+/* n / d for a denominator d in [1.75, 2.5] and n = +0 or |n| <= 0.5 (the only use: log's (m-1)/(m+1), whose numerator is
+ * never -0). Host: the IEEE operator. Device: the same correctly rounded quotient computed without hipcc's
  * generic denormal scaling and special-case fix-up (v_rcp_f32 seed, one Newton step, one exact fma
  * residual correction). Operands are normal and of moderate magnitude by construction, so the result is
- * bit-identical to `/` (tools/verify_div.hip, DESIGN.md "lean exact ops"). */
+ * bit-identical to `/` (tests/test_gpu_device_arith.py: every m - 1 over m + 1 of log and 2^30 pairs of the domain; a -0
+ * numerator would give +0 where `/` gives -0). */
 SZG_FP_FN float szg_div_moderate(float n, float d)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     /* y = RN(1 / d) (v_rcp_f32 + one Newton step: exhaustively verified, tools/verify_div.hip), q0 = RN(n y), then ONE
      * correction with the exact residual (Markstein): the correctly rounded quotient for every operand pair of this domain
-     * (the same sequence as szg_device.hpp divR0, whose verification covers it; a zero numerator gives +0 like `/`). */
+     * (the same sequence as szg_device.hpp divR0, whose verification covers it; a +0 numerator gives +0 like `/`). */
     float y = __builtin_amdgcn_rcpf(d);
     y = __builtin_fmaf(__builtin_fmaf(-d, y, 1.0f), y, y);
     float const q0 = n * y;
@@ -76,7 +82,8 @@ SZG_FP_FN float szg_expf_notnan(float x)
 #if defined(__HIP_DEVICE_COMPILE__)
     /* The two-step scaling below in ONE instruction: the first product is exact (u in (0.5, 2), |q1| <= 76), so the value is
      * u * 2^q rounded once - which is what v_ldexp_f32 returns, denormal, zero and infinite results included. Checked on
-     * gfx950 for every u in [0.5, 2) and every q in [-152, 130] (tools/verify_ldexp.hip, profiles/r02_verify_ldexp.txt). */
+     * gfx950 for every u in [0.5, 2) and every q in [-152, 130] (tools/verify_ldexp.hip, profiles/r02_verify_ldexp.txt); the
+     * device build equals the host build on a stratified sample (tests/test_gpu_device_arith.py). */
     return __builtin_ldexpf(u, qi);
 #else
     int const q1 = qi >> 1;

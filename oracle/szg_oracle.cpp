@@ -76,6 +76,7 @@
 #define GL_COS cosf
 #define GL_ASIN asinf
 #define GL_ACOS acosf
+#define GL_LOG logf
 #else
 #include "szg/fpmath.h"
 #define GL_EXP szg_expf
@@ -84,6 +85,7 @@
 #define GL_COS szg_cosf
 #define GL_ASIN szg_asinf
 #define GL_ACOS szg_acosf
+#define GL_LOG szg_logf
 #endif
 
 #include <algorithm>
@@ -1948,6 +1950,7 @@ void oracle_builtin_eval(int fn, const float* x, const float* y, float* out, siz
         case 2: out[i] = GL_SIN(x[i]); break;
         case 3: out[i] = GL_COS(x[i]); break;
         case 4: out[i] = GL_ASIN(x[i]); break;
+        case 6: out[i] = GL_LOG(x[i]); break;
         default: out[i] = GL_ACOS(x[i]); break;
         }
     }

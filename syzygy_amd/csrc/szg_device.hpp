@@ -122,15 +122,16 @@ SZG_DEV float safeSqrt(float v) { return sqrtf(fmaxf(v, 0.0f)); } // atmosphere/
 // (v_rcp_f32 / v_rsq_f32 seed, Newton, exact fma residual corrections). They return the
 // IEEE-754 correctly rounded result — bit-identical to `/` and sqrtf() — whenever their
 // operand preconditions hold, and cost ~6 / ~6 instructions; a division whose denominator's
-// reciprocal is shared costs 3. Checked on MI355X: sqrtN == sqrtf for ALL
-// binary32 inputs in its domain; divN == `/` on 4.3e9 random operand pairs with exponents
-// in [-60, 60] plus zero numerators (scratch history in DESIGN.md "lean exact ops").
+// reciprocal is shared costs 3. Checked on MI355X by tests/test_gpu_device_arith.py against
+// float64 references: sqrtN and rcpN for ALL binary32 inputs in their domains; divN on every
+// numerator significand for the all-ones and 64 random denominators and on 2^30 pairs of each
+// family of tools/verify_div.hip (the longer sweeps; history in DESIGN.md "lean exact ops").
 // They are used only under a wave-uniform `lean` flag that the kernels derive from the
 // atmosphere block and the ray (see leanAtmosphere / leanRay); otherwise the generic
 // operators are used, so results never depend on the flag.
 // ---------------------------------------------------------------------------
 // Correctly rounded reciprocal: rcpN(b) == RN(1 / b) for EVERY binary32 b with |b| in [2^-60, 2^60]
-// (tools/verify_div.hip, exhaustive on MI355X): v_rcp_f32 and one Newton step.
+// (tests/test_gpu_device_arith.py and tools/verify_div.hip, exhaustive on MI355X): v_rcp_f32 and one Newton step.
 SZG_DEV float rcpN(float b)
 {
     float const y = __builtin_amdgcn_rcpf(b);
@@ -140,8 +141,9 @@ SZG_DEV float rcpN(float b)
 // a / b given y = rcpN(b); a == +-0 or |a| in [2^-60, 2^60]. Markstein's theorem: with y the correctly rounded
 // reciprocal, q0 = RN(a * y) and the exact residual r = a - b * q0 (one fma), RN(q0 + r * y) is the correctly rounded
 // quotient, the only candidates for an exception being denominators whose significand is all ones — and those are
-// checked exhaustively against `/` together with the premise (tools/verify_div.hip: every numerator significand for the
-// 120 all-ones denominators of the domain and for 4096 random ones, plus 6.4e10 random and structured pairs).
+// checked exhaustively against RN(a / b) together with the premise (tests/test_gpu_device_arith.py: every numerator
+// significand for the 120 all-ones denominators of the domain and for 64 random ones, 5.4e9 random and structured pairs;
+// tools/verify_div.hip: 4096 random denominators and 6.4e10 pairs).
 SZG_DEV float divR(float a, float b, float y)
 {
     float const q0 = a * y;
@@ -162,7 +164,8 @@ SZG_DEV float divR0(float a, float b, float y)
     return __builtin_fmaf(r, y, q0);
 }
 // sqrt(x) for x == 0 or x in [2^-96, FLT_MAX] (NaN -> NaN): v_rsq_f32 seed, one Newton step on the exact fma residual.
-// Bit-identical to sqrtf for EVERY binary32 value of that domain (tools/verify_sqrt.hip, exhaustive on MI355X).
+// Bit-identical to sqrtf for EVERY binary32 value of that domain (tests/test_gpu_device_arith.py and tools/verify_sqrt.hip,
+// exhaustive on MI355X against RN(sqrt x) in float64).
 // The max() only matters for x == 0: rsq stays finite, so 0 * y = 0 and the correction is fma(0, h, 0) = 0.
 SZG_DEV float sqrtN(float x)
 {
@@ -190,7 +193,8 @@ template <bool LEAN> SZG_DEV float expX(float x) { return LEAN ? szg_expf_notnan
 // szg_expf (szg/fpmath.h) for x in [-86, 87], not NaN: the same reduction and polynomial, value for value. In that range the
 // clamp of the argument to [-104, 89] is the identity, q = rint(x log2 e) lies in [-125, 126] and u in (0.5, 2), so
 // u * 2^(q >> 1) and its product with 2^(q - (q >> 1)) are exact (no underflow, no overflow): (u * 2^q1) * 2^(q - q1) is
-// u * 2^q, which is what v_ldexp_f32 returns for a normal result. 9 instructions less than szg_expf_notnan.
+// u * 2^q, which is what v_ldexp_f32 returns for a normal result. 9 instructions less than szg_expf_notnan. Equal to it for
+// every x of the range (tests/test_gpu_device_arith.py).
 SZG_DEV float expInner(float x)
 {
     float const q = __builtin_rintf(x * 1.442695040888963407359924681001892137426645954152985934135449406931f);
@@ -224,7 +228,8 @@ SZG_DEV bool waveAll(bool c) { return __builtin_amdgcn_ballot_w64(!c) == 0ull; }
 // (2^-126 <= x < inf) and an exponent that is a finite number other than 0 - the same operations value for value, without
 // the selects that cannot fire there: log's denormal pre-scaling (x >= 2^-126) and its x == inf / x == 0 / x < 0 / NaN
 // cases, exp's NaN pass-through (the argument y * log x is a finite product), pow's x == 0 and y == 0 cases. The clamp of
-// exp's argument stays: x^160 underflows for most bases.
+// exp's argument stays: x^160 underflows for most bases. Equal to szg_powf on every base of [2^-20, 2) for the path's
+// exponents and on 2^28 random pairs of the precondition (tests/test_gpu_device_arith.py).
 SZG_DEV float powLean(float x, float y)
 {
     int const bits = szg_float_to_bits(x * 1.3333333333333333333333333333333333333f);

@@ -55,20 +55,45 @@ def test_pow_relative_error(y, lo, hi, rel):
     assert (np.abs(got - want) / want).max() <= rel
 
 
-def test_special_values():
+def check_special_values(evaluate):
+    """GLSL's special cases of the pinned built-ins, for an evaluator (fn, x[, y]) -> values: the host build here, the device
+    build in tests/test_gpu_device_arith.py."""
     inf, nan = np.float32(np.inf), np.float32(np.nan)
-    e = ob.builtin_eval(0, np.array([0.0, -np.inf, np.inf, nan, -104.5, 89.5], np.float32))
+    e = evaluate(0, np.array([0.0, -np.inf, np.inf, nan, -104.5, 89.5], np.float32))
     assert e[0] == 1.0 and e[1] == 0.0 and e[2] == inf and np.isnan(e[3]) and e[4] == 0.0 and e[5] == inf
-    p = ob.builtin_eval(1, np.array([0.0, 1.0, 2.0, 0.0, -1.0, 0.5], np.float32), np.array([5.0, 160.0, 0.0, 0.0, 2.0, 1.0], np.float32))
+    p = evaluate(1, np.array([0.0, 1.0, 2.0, 0.0, -1.0, 0.5], np.float32), np.array([5.0, 160.0, 0.0, 0.0, 2.0, 1.0], np.float32))
     assert p[0] == 0.0 and p[1] == 1.0 and p[2] == 1.0 and p[3] == 1.0 and np.isnan(p[4]) and abs(p[5] - 0.5) < 1e-7
-    s = ob.builtin_eval(2, np.array([0.0, 1e9, nan], np.float32))
+    s = evaluate(2, np.array([0.0, 1e9, nan], np.float32))
     assert s[0] == 0.0 and np.isnan(s[1]) and np.isnan(s[2])
-    c = ob.builtin_eval(3, np.array([0.0], np.float32))
+    c = evaluate(3, np.array([0.0], np.float32))
     assert c[0] == 1.0
-    a = ob.builtin_eval(4, np.array([1.0, -1.0, 1.5, 0.0], np.float32))
+    a = evaluate(4, np.array([1.0, -1.0, 1.5, 0.0], np.float32))
     assert abs(a[0] - np.pi / 2) < 2e-7 and abs(a[1] + np.pi / 2) < 2e-7 and np.isnan(a[2]) and a[3] == 0.0
-    k = ob.builtin_eval(5, np.array([1.0, -1.0, 0.0, -1.5], np.float32))
+    k = evaluate(5, np.array([1.0, -1.0, 0.0, -1.5], np.float32))
     assert k[0] == 0.0 and abs(k[1] - np.pi) < 4e-7 and abs(k[2] - np.pi / 2) < 2e-7 and np.isnan(k[3])
+
+
+def test_special_values():
+    check_special_values(ob.builtin_eval)
+
+
+# The largest errors of the host build over EVERY binary32 input of each range (-O2 -mfma -ffp-contract=off, against float64),
+# and the bounds fpmath.h states from them (the device build gives the same bits: tests/test_gpu_device_arith.py sweeps every
+# input on the GPU). sin and cos are worst next to their zeros, where a relative bound is hardest to meet: 5.79 ULP near
+# 3pi/2 and 3pi, inside the sky-view LUT's azimuth range [-pi/2, 3pi/2]; their absolute error stays far inside GLSL's 2^-11.
+@pytest.mark.parametrize("fn,x,ref,bound", [
+    (3, "0x1.2d97c8p+2", np.cos, 5.8),    # cos(~3pi/2): 5.793 ULP, the maximum on [-pi/2, 3pi/2] and on [-10, 10]
+    (2, "-0x1.2d97c8p+3", np.sin, 5.8),   # sin(~-3pi): 5.793 ULP, the maximum on [-10, 10]
+    (3, "-0x1.2eb5c4p+1", np.cos, 1.6),   # 1.551 ULP, the maximum on [-pi, pi]
+    (6, "0x1.21bd82p+0", np.log, 2.85),   # 2.845 ULP, the maximum on (0, FLT_MAX]
+    (4, "0x1.00dfd2p-1", np.arcsin, 2.4), # 2.356 ULP, the maximum on [-1, 1]
+    (5, "-0x1.00dfd2p-1", np.arccos, 1.3),  # 1.272 ULP, the maximum on [-1, 1]
+    (0, "0x1.da3336p+5", np.exp, 1.0),    # 0.988 ULP, the maximum on [-87, 88]
+])
+def test_worst_inputs_of_the_exhaustive_sweeps(fn, x, ref, bound):
+    xs = np.array([float.fromhex(x)], np.float32)
+    err = ulp_error(ob.builtin_eval(fn, xs), ref(xs.astype(np.float64)))[0]
+    assert bound - 0.06 < err <= bound
 
 
 def test_pinned_and_libm_builds_agree_to_a_few_ulp():
