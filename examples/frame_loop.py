@@ -8,8 +8,14 @@
     SkyViewComputePipeline::recordDrawCommands                      transmittance LUT, sky-view LUT, composite
     --debug-lines: a box per instance + the shadow bounds, in green renderer.cpp:355-365, :417-427, :445-476
     OETF on the presented image                                     editor.cpp:303-340
+    --present WxH[:format]: the blit onto a swapchain-sized image   editor.cpp:355-361 (szg/present.h), on the GPU
 
     python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm [--debug-lines [--line-width 2]]
+                                  [--present 1280x720[:rgba8|bgra8|a2b10g10r10]]
+
+Without --present the 16-bit scene colour is copied to the host and the PPM holds its high bytes; with it every frame ends
+with the reference's LINEAR blit onto a WxH image of the given swapchain format (default rgba8) and the PPM is that image
+(maxval 255, or 1023 for a2b10g10r10).
 
 Needs an MI355X (no CPU fallback). Everything on the GPU is enqueued on one stream; the host only ticks the scene.
 """
@@ -26,7 +32,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--width", type=int, default=1280)
@@ -35,7 +41,9 @@ def main():
     ap.add_argument("--out", default="", help="write the last frame as a binary PPM (8 bit)")
     ap.add_argument("--debug-lines", action="store_true", help="the editor's Debug Lines switch (engineui.cpp:95-109)")
     ap.add_argument("--line-width", type=float, default=1.0)
-    args = ap.parse_args()
+    ap.add_argument("--present", default="", metavar="WxH[:format]",
+                    help="end every frame with the blit onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) and write --out from it")
+    args = ap.parse_args(argv)
 
     import torch
 
@@ -84,6 +92,11 @@ def main():
     rect = pl.rect(W, H)
     debug_lines = pl.DebugLines()  # Renderer::m_debugLines, DEBUGLINES_CAPACITY vertices (renderer.hpp:103)
     debug_lines.enabled, debug_lines.lineWidth = args.debug_lines, args.line_width
+    try:
+        present = pl.parse_present_option(args.present) if args.present else None  # (width, height, format)
+    except ValueError as e:
+        ap.error(f"--present {e}")
+    swapchain = pl.swapchain_image(*present) if present else None
 
     t_start = time.perf_counter()
     elapsed, dt = 0.0, 1.0 / 60.0
@@ -114,13 +127,18 @@ def main():
         debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423
         debug_lines.recordDraw(None, 0, target, rect, cameras)  # renderer.cpp:425-427, :445-476 (only when enabled)
         pl.recordOETF(None, target, W, H)
+        if present:  # editor.cpp:355-361: the whole scene onto the whole swapchain image, LINEAR
+            pl.record_copy_image_to_image(None, target, swapchain, dstFormat=present[2])
         elapsed += dt
     torch.cuda.synchronize()
     wall = time.perf_counter() - t_start
     image = target.color_numpy()
     print(f"{args.frames} frames of {W}x{H}: {wall / args.frames * 1e3:.2f} ms per frame including host scene prep; "
           f"mean display value {image[..., :3].mean() / 65535.0:.3f}")
-    if args.out:
+    if args.out and present:
+        pl.write_presented_ppm(args.out, swapchain.cpu().numpy(), present[2])
+        print("wrote", args.out, f"({present[0]}x{present[1]}, presented on the GPU)")
+    elif args.out:
         with open(args.out, "wb") as f:
             f.write(f"P6 {W} {H} 255\n".encode())
             f.write((image[..., :3] >> 8).astype(np.uint8).tobytes())

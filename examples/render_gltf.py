@@ -3,6 +3,10 @@
 whole path: shadow raster, G-buffer raster, lights, transmittance + sky-view LUTs, composite, OETF.
 
     python examples/render_gltf.py [model.glb | model.gltf] --out /tmp/gltf.ppm [--embedded-images]
+                                   [--present 1920x1080[:rgba8|bgra8|a2b10g10r10]]
+
+--present ends the frame as the reference's editor does (editor.cpp:355-361, include/szg/present.h): the scene colour is
+blitted on the GPU, LINEAR, onto a swapchain-sized image of the given format, and --out is written from that image.
 
 Without a file a textured sphere is written first (the reference's own assets/sphere.glb is a git-LFS pointer in this
 checkout). Meshes are scaled to 8 m and set on the editor's floor plane. Needs an MI355X (no CPU fallback).
@@ -42,14 +46,16 @@ def write_sphere(path):
         f.write(b.glb())
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("path", nargs="?", default="")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--out", default="")
     ap.add_argument("--embedded-images", action="store_true", help="also decode images stored in GLB buffer views (the reference does not)")
-    args = ap.parse_args()
+    ap.add_argument("--present", default="", metavar="WxH[:format]",
+                    help="blit the frame onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) on the GPU and write --out from it")
+    args = ap.parse_args(argv)
 
     import torch
 
@@ -114,11 +120,21 @@ def main():
     deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
     sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     pl.recordOETF(None, target, W, H)
+    try:
+        present = pl.parse_present_option(args.present) if args.present else None  # (width, height, format)
+    except ValueError as e:
+        ap.error(f"--present {e}")
+    if present:
+        swapchain = pl.swapchain_image(*present)
+        pl.record_copy_image_to_image(None, target, swapchain, dstFormat=present[2])
     torch.cuda.synchronize()
     image = target.color_numpy()
     covered = float((target.depth.cpu().numpy() > 0).mean())
     print(f"rendered {W}x{H}: geometry covers {covered:.1%} of the frame, mean display value {image[..., :3].mean() / 65535.0:.3f}")
-    if args.out:
+    if args.out and present:
+        pl.write_presented_ppm(args.out, swapchain.cpu().numpy(), present[2])
+        print("wrote", args.out, f"({present[0]}x{present[1]}, presented on the GPU)")
+    elif args.out:
         with open(args.out, "wb") as f:
             f.write(f"P6 {W} {H} 255\n".encode())
             f.write((image[..., :3] >> 8).astype(np.uint8).tobytes())

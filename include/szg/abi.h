@@ -26,6 +26,9 @@
 extern "C" {
 #endif
 
+/* Counts INCOMPATIBLE changes: a struct layout, a signature or the meaning of an existing value. Purely additive steps - a new
+ * entry point, new szg_format values behind the existing ones (szg/present.h) - keep it: a caller built against the
+ * previous header still runs, and a loader that needs the new symbol finds out by looking it up. */
 #define SZG_ABI_VERSION 2
 
 /* ------------------------------------------------------------------------- */
@@ -174,7 +177,11 @@ typedef enum szg_format
     SZG_FORMAT_RGBA16_SFLOAT = 1, /* 8 B/texel  : G-buffer diffuse/specular/normal/ORM */
     SZG_FORMAT_RGBA32_SFLOAT = 2, /* 16 B/texel : G-buffer worldPosition, both LUTs, debug colour */
     SZG_FORMAT_RGBA16_UNORM = 3,  /* 8 B/texel  : scene colour */
-    SZG_FORMAT_D32_SFLOAT = 4     /* 4 B/texel  : scene depth, shadow maps (reverse-Z, 0 = far) */
+    SZG_FORMAT_D32_SFLOAT = 4,    /* 4 B/texel  : scene depth, shadow maps (reverse-Z, 0 = far) */
+    /* destinations of the present pass only (szg/present.h; the swapchain formats of editor/swapchain.cpp:99-103) */
+    SZG_FORMAT_RGBA8_UNORM = 5,        /* 4 B/texel : bytes R, G, B, A */
+    SZG_FORMAT_BGRA8_UNORM = 6,        /* 4 B/texel : bytes B, G, R, A */
+    SZG_FORMAT_A2B10G10R10_UNORM = 7   /* 4 B/texel : one little-endian dword, R bits 0-9, G 10-19, B 20-29, A 30-31 */
 } szg_format;
 
 typedef struct szg_image
@@ -190,7 +197,8 @@ typedef struct szg_image
  * gbufferOffset = 0 (lights.comp:112 with deferred.cpp:764, :778-787; camera.comp has no offset at all,
  * skyview.cpp:658-665): whatever the offset says, it shades the top-left width x height texels. A non-zero x or y
  * is therefore a request this path does not serve: every record_* entry point refuses it with
- * SZG_ERR_INVALID_ARGUMENT instead of silently rendering somewhere else. */
+ * SZG_ERR_INVALID_ARGUMENT instead of silently rendering somewhere else. The one call that honours the offset is the
+ * present pass (szg/present.h), as the reference's blit does (editor.cpp:355-361). */
 typedef struct szg_rect
 {
     int32_t x, y;

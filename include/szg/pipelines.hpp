@@ -13,6 +13,8 @@
 //   DeferredShadingPipeline     pipelines/deferred.hpp:23  szg::DeferredShadingPipeline
 //   SkyViewComputePipeline      pipelines/skyview.hpp:24   szg::SkyViewComputePipeline
 //   DebugLineGraphicsPipeline   pipelines.hpp:238-268      szg::DebugLineGraphicsPipeline (szg/debuglines.h)
+//   recordCopyImageToImage      imageoperations.cpp:45-176 szg::recordCopyImageToImage (szg/present.h)
+//   Editor::endFrame's tail     editor.cpp:303-361         szg::recordPresent
 //   std::span<MeshInstanced const> sceneGeometry           szg_fill_scene const* (synthetic)
 //
 // Error behaviour follows the reference: construction failures give an invalid object /
@@ -29,6 +31,7 @@
 
 #include "szg/abi.h"
 #include "szg/debuglines.h"
+#include "szg/present.h"
 #include "szg/raster.h"
 #include "szg/host.h"
 
@@ -469,4 +472,74 @@ struct DebugLineGraphicsPipeline
     szg_debug_lines_t* m_handle{nullptr};
     int m_lastStatus{SZG_OK};
 };
+// ---- present pass (szg/present.h) ----
+// Free functions, as in the reference. They return the C-ABI status, log a negative one like the pipelines' record calls
+// and keep it in lastPresentStatus() (per thread).
+namespace detail
+{
+inline auto presentStatus() -> int&
+{
+    thread_local int status{SZG_OK};
+    return status;
+}
+} // namespace detail
+[[nodiscard]] inline auto lastPresentStatus() -> int { return detail::presentStatus(); }
+
+// imageoperations.cpp:87-119: the VkRect2D form, VK_FILTER_LINEAR (:81). Scales srcSize of `source` (RGBA16_UNORM) onto
+// dstSize of `destination` (RGBA8 / BGRA8 / A2B10G10R10) and converts; both offsets are honoured. `encode` is this
+// library's addition: a transfer function applied to the taps, so that the source keeps its linear values.
+inline auto recordCopyImageToImage(hipStream_t cmd, szg_image const& source, szg_image const& destination, szg_rect srcSize,
+                                   szg_rect dstSize, uint32_t encode = SZG_PRESENT_ENCODE_NONE) -> int
+{
+    szg_present_info const info{srcSize, dstSize, SZG_FILTER_LINEAR, encode};
+    return detail::note(szg_record_present(cmd, &source, &destination, &info), "szg_record_present", detail::presentStatus());
+}
+// imageoperations.cpp:141-176: the form behind Image::recordCopyEntire / recordCopyRect (image.cpp:185-229), corners instead
+// of rectangles and VK_FILTER_NEAREST (:169). The aspect mask is dropped (colour only); a max corner below its min corner (a
+// flipped blit, which a szg_rect cannot express) is refused.
+struct Offset2D
+{
+    int32_t x, y;
+};
+inline auto recordCopyImageToImage(hipStream_t cmd, szg_image const& src, szg_image const& dst, Offset2D srcMin, Offset2D srcMax,
+                                   Offset2D dstMin, Offset2D dstMax) -> int
+{
+    if (srcMax.x < srcMin.x || srcMax.y < srcMin.y || dstMax.x < dstMin.x || dstMax.y < dstMin.y)
+    {
+        std::fprintf(stderr, "[szg] recordCopyImageToImage: flipped regions are not supported\n");
+        return detail::presentStatus() = SZG_ERR_INVALID_ARGUMENT;
+    }
+    szg_present_info const info{
+        szg_rect{srcMin.x, srcMin.y, static_cast<uint32_t>(srcMax.x - srcMin.x), static_cast<uint32_t>(srcMax.y - srcMin.y)},
+        szg_rect{dstMin.x, dstMin.y, static_cast<uint32_t>(dstMax.x - dstMin.x), static_cast<uint32_t>(dstMax.y - dstMin.y)},
+        SZG_FILTER_NEAREST, SZG_PRESENT_ENCODE_NONE};
+    return detail::note(szg_record_present(cmd, &src, &dst, &info), "szg_record_present", detail::presentStatus());
+}
+
+// What Editor::endFrame records once the frame is drawn (editor.cpp:303-361): the OETF in place on the scene texture, then
+// the LINEAR blit of sourceSubregion onto the WHOLE swapchain image. The reference dispatches the OETF over the top-left
+// SWAPCHAIN extent of the scene texture, not over sourceSubregion (editor.cpp:328-337): with an offset or a scaled subregion
+// the encoded texels are not the presented ones. That is the reference's behaviour and is kept on purpose; the extent is
+// clamped to the texture, as the shader's out-of-range stores are dropped.
+inline auto recordPresent(hipStream_t cmd, SceneTexture& sceneTexture, szg_rect sourceSubregion, szg_image const& swapchainImage,
+                          uint32_t gammaFunction = SZG_OETF_SRGB) -> int
+{
+    szg_image const& color = sceneTexture.color();
+    uint32_t const w = swapchainImage.width < color.width ? swapchainImage.width : color.width;
+    uint32_t const h = swapchainImage.height < color.height ? swapchainImage.height : color.height;
+    if (detail::note(szg_record_oetf(cmd, &color, w, h, gammaFunction), "szg_record_oetf", detail::presentStatus()) != SZG_OK)
+    {
+        return detail::presentStatus();
+    }
+    return recordCopyImageToImage(cmd, color, swapchainImage, sourceSubregion,
+                                  szg_rect{0, 0, swapchainImage.width, swapchainImage.height});
+}
+// The same frame end in one pass: the transfer function is applied to the blit's taps (szg/present.h ENCODE), exactly the
+// texels that are presented, and the scene texture keeps its linear values. 12 B/px at 1:1 instead of 16 + 12.
+inline auto recordPresentEncoded(hipStream_t cmd, SceneTexture const& sceneTexture, szg_rect sourceSubregion,
+                                 szg_image const& swapchainImage, uint32_t encode = SZG_OETF_SRGB) -> int
+{
+    return recordCopyImageToImage(cmd, sceneTexture.color(), swapchainImage, sourceSubregion,
+                                  szg_rect{0, 0, swapchainImage.width, swapchainImage.height}, encode);
+}
 } // namespace szg

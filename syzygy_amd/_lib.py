@@ -49,6 +49,11 @@ def lib():
         abi.bind(handle, abi.RASTER_FUNCTIONS)
         abi.bind(handle, abi.ASSET_FUNCTIONS)
         abi.bind(handle, abi.DEBUGLINE_FUNCTIONS)
+        try:
+            abi.bind(handle, abi.PRESENT_FUNCTIONS)
+        except AttributeError as e:
+            # additive entry points do not move the ABI version (include/szg/abi.h): an older build of the same version lacks them
+            raise RuntimeError(f"{path} predates include/szg/present.h ({e}); rebuild the library") from e
         _LIB = handle
     return _LIB
 

@@ -29,12 +29,19 @@ SZG_FORMAT_RGBA16_SFLOAT = 1
 SZG_FORMAT_RGBA32_SFLOAT = 2
 SZG_FORMAT_RGBA16_UNORM = 3
 SZG_FORMAT_D32_SFLOAT = 4
+# destinations of the present pass (include/szg/present.h)
+SZG_FORMAT_RGBA8_UNORM = 5
+SZG_FORMAT_BGRA8_UNORM = 6
+SZG_FORMAT_A2B10G10R10_UNORM = 7
 
 TEXEL_BYTES = {
     SZG_FORMAT_RGBA16_SFLOAT: 8,
     SZG_FORMAT_RGBA32_SFLOAT: 16,
     SZG_FORMAT_RGBA16_UNORM: 8,
     SZG_FORMAT_D32_SFLOAT: 4,
+    SZG_FORMAT_RGBA8_UNORM: 4,
+    SZG_FORMAT_BGRA8_UNORM: 4,
+    SZG_FORMAT_A2B10G10R10_UNORM: 4,
 }
 
 
@@ -526,6 +533,21 @@ DEBUGLINE_FUNCTIONS = {
     "szg_debug_lines_create": (C.c_int, [P(VP), U32, C.c_int]),
     "szg_debug_lines_destroy": (None, [VP]),
     "szg_debug_lines_record": (C.c_int, [VP, VP, C.c_float, Rect, P(RowTile), P(SceneTexture), U32, VP, VP, U32]),
+}
+
+# include/szg/present.h
+SZG_PRESENT_MAX_EXTENT = 16384
+SZG_FILTER_NEAREST = 0
+SZG_FILTER_LINEAR = 1
+SZG_PRESENT_ENCODE_NONE = 0xFFFFFFFF
+
+
+class PresentInfo(C.Structure):
+    _fields_ = [("src_region", Rect), ("dst_region", Rect), ("filter", U32), ("encode", U32)]
+
+
+PRESENT_FUNCTIONS = {
+    "szg_record_present": (C.c_int, [VP, P(Image), P(Image), P(PresentInfo)]),
 }
 
 

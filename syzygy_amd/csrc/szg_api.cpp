@@ -60,6 +60,9 @@ unsigned texel_bytes(unsigned fmt)
     case SZG_FORMAT_RGBA32_SFLOAT:
         return 16;
     case SZG_FORMAT_D32_SFLOAT:
+    case SZG_FORMAT_RGBA8_UNORM:
+    case SZG_FORMAT_BGRA8_UNORM:
+    case SZG_FORMAT_A2B10G10R10_UNORM:
         return 4;
     default:
         return 0;
@@ -1414,6 +1417,108 @@ int szg_record_oetf(void* stream, const szg_image* image, uint32_t width, uint32
     SZG_HIP(szg::launch_oetf(static_cast<hipStream_t>(stream), *image, width, height, table));
     return SZG_OK;
 }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// Present pass (include/szg/present.h): editor.cpp:355-361 -> imageoperations.cpp:45-119
+// ---------------------------------------------------------------------------
+namespace
+{
+// One image of the blit: present, of an accepted format, not above the extent cap, rows inside the pitch, and the region
+// inside the image. Everything here runs on the host, before anything is launched.
+bool check_present_image(const szg_image* im, const szg_rect& r, bool isSource, const char* name)
+{
+    if (im == nullptr || im->data == nullptr)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s image or its data is NULL", name);
+        return false;
+    }
+    bool const formatOk = isSource ? im->format == SZG_FORMAT_RGBA16_UNORM
+                                   : (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_BGRA8_UNORM ||
+                                      im->format == SZG_FORMAT_A2B10G10R10_UNORM);
+    if (!formatOk)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT,
+             isSource ? "szg_record_present: %s format %u, the source must be RGBA16_UNORM"
+                      : "szg_record_present: %s format %u, the destination must be RGBA8_UNORM, BGRA8_UNORM or A2B10G10R10_UNORM",
+             name, im->format);
+        return false;
+    }
+    if (im->width > SZG_PRESENT_MAX_EXTENT || im->height > SZG_PRESENT_MAX_EXTENT)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s image %ux%u exceeds %u texels", name, im->width, im->height,
+             SZG_PRESENT_MAX_EXTENT);
+        return false;
+    }
+    unsigned const tb = texel_bytes(im->format);
+    if ((size_t)im->pitch_bytes < (size_t)im->width * tb || im->pitch_bytes % tb != 0u ||
+        reinterpret_cast<uintptr_t>(im->data) % tb != 0u)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s pitch %u / alignment invalid for %u texels of %u bytes", name,
+             im->pitch_bytes, im->width, tb);
+        return false;
+    }
+    if (r.x < 0 || r.y < 0 || (uint64_t)r.x + r.width > im->width || (uint64_t)r.y + r.height > im->height)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s region (%d, %d) %ux%u leaves the %ux%u image", name, r.x, r.y,
+             r.width, r.height, im->width, im->height);
+        return false;
+    }
+    return true;
+}
+// the bytes an image's texels occupy: [begin, end)
+void image_range(const szg_image& im, uintptr_t& begin, uintptr_t& end)
+{
+    begin = reinterpret_cast<uintptr_t>(im.data);
+    size_t const bytes = im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format);
+    end = begin + bytes;
+}
+} // namespace
+
+extern "C" int szg_record_present(void* stream, const szg_image* src, const szg_image* dst, const szg_present_info* info)
+{
+    if (info == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: info is NULL");
+    }
+    if (!check_present_image(src, info->src_region, true, "source") || !check_present_image(dst, info->dst_region, false, "destination"))
+    {
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
+    if (info->filter != SZG_FILTER_NEAREST && info->filter != SZG_FILTER_LINEAR)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: unknown filter %u", info->filter);
+    }
+    if (info->encode != SZG_PRESENT_ENCODE_NONE && info->encode != SZG_OETF_PURE_GAMMA && info->encode != SZG_OETF_SRGB)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: unknown encode %u", info->encode);
+    }
+    uintptr_t sb, se, db, de;
+    image_range(*src, sb, se);
+    image_range(*dst, db, de);
+    if (sb < de && db < se)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: source and destination images overlap in memory");
+    }
+    if (info->src_region.width == 0u || info->src_region.height == 0u || info->dst_region.width == 0u || info->dst_region.height == 0u)
+    {
+        return SZG_OK; // nothing to sample or nothing to cover
+    }
+    const unsigned short* table = nullptr;
+    if (info->encode != SZG_PRESENT_ENCODE_NONE)
+    {
+        int const rc = oetf_table(static_cast<hipStream_t>(stream), info->encode, &table);
+        if (rc != SZG_OK)
+        {
+            return rc;
+        }
+    }
+    SZG_HIP(szg::launch_present(static_cast<hipStream_t>(stream), *src, *dst, *info, table));
+    return SZG_OK;
+}
+
+extern "C" {
 
 int szg_compose_rowtiles(void* stream, const void* gathered, size_t tile_stride_bytes, uint32_t nranks, uint32_t block_rows,
                          const szg_image* dst, uint32_t width, uint32_t height)

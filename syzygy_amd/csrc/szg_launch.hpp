@@ -6,6 +6,7 @@
 
 #include "szg/abi.h"
 #include "szg/debuglines.h"
+#include "szg/present.h"
 #include "szg/raster.h"
 
 namespace szg
@@ -214,4 +215,9 @@ hipError_t debug_lines_scan_temp_bytes(unsigned lineCapacity, size_t& bytes);
 hipError_t launch_debug_lines(hipStream_t s, const szg_scene_texture& scene, unsigned W, unsigned H, TileArgs tile,
                               const szg_camera_packed* d_cam, unsigned camIndex, const szg_vertex_packed* d_vertices,
                               unsigned lineCount, float lineWidth, DebugLineBuffers& b);
+
+// ---- present pass (kernels_present.hip, include/szg/present.h) ----
+// Arguments already validated; `table` is the OETF table of info.encode, or nullptr for SZG_PRESENT_ENCODE_NONE.
+hipError_t launch_present(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_present_info& info,
+                          const unsigned short* table);
 } // namespace szg

@@ -8,6 +8,7 @@ Names, argument order and meaning follow the reference:
   SkyViewComputePipeline    renderer/pipelines/skyview.hpp:24-51
   DebugLines                renderer/pipelines/debuglines.hpp:22-68
   DebugLineGraphicsPipeline renderer/pipelines.hpp:238-268
+  record_copy_image_to_image / record_present   renderer/imageoperations.cpp:45-176, editor/editor.cpp:303-361
 with `cmd` (VkCommandBuffer) replaced by a HIP stream handle and Vulkan images by
 linear device buffers. torch is used only to own device memory and streams.
 """
@@ -164,6 +165,124 @@ def recordOETF(cmd, sceneTexture, width, height, transferFunction=abi.SZG_OETF_S
     editorconfig.hpp:13)."""
     im = sceneTexture.abi().color
     check(lib().szg_record_oetf(_stream_handle(cmd), C.byref(im), int(width), int(height), int(transferFunction)))
+
+
+# ---------------------------------------------------------------------------
+# Present pass (include/szg/present.h)
+# ---------------------------------------------------------------------------
+def _as_rect(r):
+    """An abi.Rect, or (x, y, width, height)."""
+    return r if isinstance(r, abi.Rect) else abi.Rect(int(r[0]), int(r[1]), int(r[2]), int(r[3]))
+
+
+def _strided_image(tensor, fmt, channels):
+    """szg_image over a torch tensor whose rows may be padded: [h, w, channels] (channels > 1) or [h, w]; the pitch is the
+    row stride, the texels of a row are contiguous."""
+    want = 3 if channels > 1 else 2
+    if tensor.dim() != want or (channels > 1 and (tensor.shape[2] != channels or tensor.stride(2) != 1)) or \
+            tensor.stride(1) != channels:
+        raise ValueError(f"expected a tensor of shape [h, w{', %d' % channels if channels > 1 else ''}] with contiguous rows, "
+                         f"got shape {tuple(tensor.shape)} strides {tuple(tensor.stride())}")
+    im = abi.Image()
+    im.data = tensor.data_ptr()
+    im.height, im.width = int(tensor.shape[0]), int(tensor.shape[1])
+    im.pitch_bytes = int(tensor.stride(0)) * tensor.element_size() if im.height > 1 else im.width * abi.TEXEL_BYTES[fmt]
+    im.format = fmt
+    return im
+
+
+PRESENT_FORMAT_NAMES = {"rgba8": abi.SZG_FORMAT_RGBA8_UNORM, "bgra8": abi.SZG_FORMAT_BGRA8_UNORM,
+                        "a2b10g10r10": abi.SZG_FORMAT_A2B10G10R10_UNORM}
+
+
+def parse_present_option(text):
+    """'WxH[:format]' (the examples' --present switch) -> (width, height, szg_format); format defaults to rgba8."""
+    extent, _, name = text.partition(":")
+    w, _, h = extent.lower().partition("x")
+    name = name or "rgba8"
+    if not (w.isdigit() and h.isdigit() and int(w) > 0 and int(h) > 0) or name not in PRESENT_FORMAT_NAMES:
+        raise ValueError(f"{text!r}: expected WxH[:{'|'.join(PRESENT_FORMAT_NAMES)}]")
+    return int(w), int(h), PRESENT_FORMAT_NAMES[name]
+
+
+def swapchain_image(width, height, fmt=abi.SZG_FORMAT_RGBA8_UNORM, device="cuda:0"):
+    """A tensor in the layout of a swapchain image of `fmt`: uint8 [h, w, 4] for the 8-bit formats, int32 [h, w] for
+    A2B10G10R10_UNORM. What record_copy_image_to_image / record_present take as destination."""
+    if fmt == abi.SZG_FORMAT_A2B10G10R10_UNORM:
+        return torch.zeros((int(height), int(width)), dtype=torch.int32, device=device)
+    return torch.zeros((int(height), int(width), 4), dtype=torch.uint8, device=device)
+
+
+def write_presented_ppm(path, presented, fmt):
+    """A swapchain image on the host (numpy uint8 [h, w, 4] or int32 [h, w]) as a binary PPM of its R, G, B: maxval 255, or
+    1023 (two bytes per sample, most significant first) for A2B10G10R10_UNORM."""
+    h, w = presented.shape[:2]
+    with open(path, "wb") as f:
+        if fmt == abi.SZG_FORMAT_A2B10G10R10_UNORM:
+            word = presented.view(np.uint32)
+            rgb = np.stack([word & 0x3FF, (word >> 10) & 0x3FF, (word >> 20) & 0x3FF], axis=-1)
+            f.write(f"P6 {w} {h} 1023\n".encode())
+            f.write(rgb.astype(">u2").tobytes())
+        else:
+            order = [2, 1, 0] if fmt == abi.SZG_FORMAT_BGRA8_UNORM else [0, 1, 2]
+            f.write(f"P6 {w} {h} 255\n".encode())
+            f.write(np.ascontiguousarray(presented[..., order]).tobytes())
+
+
+def present_images(source, destination, dstFormat=None):
+    """(szg_image of the RGBA16_UNORM source, szg_image of the destination). `source`: a SceneTexture or an int16 / uint16
+    tensor [h, w, 4]. `destination`: a uint8 tensor [h, w, 4] (RGBA8_UNORM, or BGRA8_UNORM with dstFormat) or an int32
+    tensor [h, w] (A2B10G10R10_UNORM)."""
+    color = source.color if isinstance(source, SceneTexture) else source
+    if color.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        raise ValueError(f"the source must hold 16-bit codes, got {color.dtype}")
+    src = _strided_image(color, abi.SZG_FORMAT_RGBA16_UNORM, 4)
+    if destination.dtype == torch.uint8:
+        fmt = abi.SZG_FORMAT_RGBA8_UNORM if dstFormat is None else int(dstFormat)
+        if fmt not in (abi.SZG_FORMAT_RGBA8_UNORM, abi.SZG_FORMAT_BGRA8_UNORM):
+            raise ValueError(f"a uint8 destination is RGBA8_UNORM or BGRA8_UNORM, not format {fmt}")
+        dst = _strided_image(destination, fmt, 4)
+    elif destination.dtype == torch.int32:
+        if dstFormat not in (None, abi.SZG_FORMAT_A2B10G10R10_UNORM):
+            raise ValueError(f"an int32 destination is A2B10G10R10_UNORM, not format {dstFormat}")
+        dst = _strided_image(destination, abi.SZG_FORMAT_A2B10G10R10_UNORM, 1)
+    else:
+        raise ValueError(f"the destination must be uint8 [h, w, 4] or int32 [h, w], got {destination.dtype}")
+    return src, dst
+
+
+def record_copy_image_to_image(cmd, source, destination, srcRegion=None, dstRegion=None, filter=abi.SZG_FILTER_LINEAR,
+                               encode=abi.SZG_PRESENT_ENCODE_NONE, dstFormat=None):
+    """imageoperations.cpp:87-119 (LINEAR, the VkRect2D form) and :141-176 (filter=SZG_FILTER_NEAREST, the form behind
+    Image::recordCopyEntire / recordCopyRect): blit `srcRegion` of the RGBA16_UNORM `source` onto `dstRegion` of
+    `destination`, scaling and converting the format by the rule of include/szg/present.h. Regions are abi.Rect or
+    (x, y, width, height), offsets honoured; None is the whole image. `encode` applies a transfer function to the taps and
+    leaves the source linear."""
+    src, dst = present_images(source, destination, dstFormat)
+    info = abi.PresentInfo()
+    info.src_region = _as_rect(srcRegion) if srcRegion is not None else abi.Rect(0, 0, src.width, src.height)
+    info.dst_region = _as_rect(dstRegion) if dstRegion is not None else abi.Rect(0, 0, dst.width, dst.height)
+    info.filter = int(filter)
+    info.encode = int(encode)
+    check(lib().szg_record_present(_stream_handle(cmd), C.byref(src), C.byref(dst), C.byref(info)))
+
+
+def record_present(cmd, sceneTexture, sourceSubregion, swapchainImage, gammaFunction=abi.SZG_OETF_SRGB, encodeInBlit=False,
+                   dstFormat=None):
+    """What Editor::endFrame records after the frame is drawn (editor.cpp:303-361): the OETF in place over the top-left
+    DESTINATION extent of the scene texture (the reference dispatches it over the swapchain extent, not over
+    sourceSubregion: editor.cpp:328-337; kept on purpose, clamped to the texture as the shader's stores are), then the LINEAR
+    blit of `sourceSubregion` onto the whole `swapchainImage`. With encodeInBlit the transfer function is applied to the
+    blit's taps instead and the scene texture keeps its linear values (12 B/px at 1:1 instead of 16 + 12)."""
+    src, dst = present_images(sceneTexture, swapchainImage, dstFormat)
+    if encodeInBlit:
+        encode = int(gammaFunction)
+    else:
+        encode = abi.SZG_PRESENT_ENCODE_NONE
+        check(lib().szg_record_oetf(_stream_handle(cmd), C.byref(src), min(dst.width, src.width), min(dst.height, src.height),
+                                    int(gammaFunction)))
+    info = abi.PresentInfo(_as_rect(sourceSubregion), abi.Rect(0, 0, dst.width, dst.height), abi.SZG_FILTER_LINEAR, encode)
+    check(lib().szg_record_present(_stream_handle(cmd), C.byref(src), C.byref(dst), C.byref(info)))
 
 
 class DeferredShadingPipeline:
