@@ -9,9 +9,17 @@
     --debug-lines: a box per instance + the shadow bounds, in green renderer.cpp:355-365, :417-427, :445-476
     OETF on the presented image                                     editor.cpp:303-340
     --present WxH[:format]: the blit onto a swapchain-sized image   editor.cpp:355-361 (szg/present.h), on the GPU
+    --pipeline compute-collection[:NAME]: the editor's other        renderer.cpp:431-438 (szg/compute_collection.h)
+      rendering pipeline instead of the deferred one
 
     python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm [--debug-lines [--line-width 2]]
                                   [--present 1280x720[:rgba8|bgra8|a2b10g10r10]]
+                                  [--pipeline compute-collection[:booleanpush|gradient_color|sparse_push_constant|matrix_color]]
+
+--pipeline mirrors the editor's "Deferred" / "Compute Collection" switch (ui/engineui.cpp:19-22). With compute-collection
+the frame uploads and fills the debug-line list as before, then records ONE program of the collection over the scene colour
+(default gradient_color) with a visible block (abi.COMPUTE_COLLECTION_EXAMPLE_VALUES): no shadow, G-buffer, light, atmosphere
+or debug-line launches. The OETF and --present follow as in the editor.
 
 Without --present the 16-bit scene colour is copied to the host and the PPM holds its high bytes; with it every frame ends
 with the reference's LINEAR blit onto a WxH image of the given swapchain format (default rgba8) and the PPM is that image
@@ -43,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--line-width", type=float, default=1.0)
     ap.add_argument("--present", default="", metavar="WxH[:format]",
                     help="end every frame with the blit onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) and write --out from it")
+    ap.add_argument("--pipeline", default="deferred", metavar="deferred|compute-collection[:NAME]",
+                    help="the rendering pipeline of Renderer::recordDraw (renderer.cpp:379-439)")
     args = ap.parse_args(argv)
 
     import torch
@@ -50,6 +60,10 @@ def main(argv=None):
     from syzygy_amd import abi, lib, meshes, pipelines as pl, scene
 
     W, H = args.width, args.height
+    try:
+        pipeline, shader = pl.parse_pipeline_option(args.pipeline)
+    except ValueError as e:
+        ap.error(f"--pipeline {e}")
     # ---- scene: the editor's start-up scene, its cubes animated (editor.cpp:500-545) -----------------------------
     material = meshes.default_material()
     cv, ci = meshes.cube_mesh()
@@ -97,6 +111,11 @@ def main(argv=None):
     except ValueError as e:
         ap.error(f"--present {e}")
     swapchain = pl.swapchain_image(*present) if present else None
+    collection = None
+    if pipeline == "compute-collection":
+        collection = pl.ComputeCollectionPipeline()  # Renderer::m_genericComputePipeline
+        collection.selectShaderByName(shader)
+        collection.writeExampleValues()
 
     t_start = time.perf_counter()
     elapsed, dt = 0.0, 1.0 / 60.0
@@ -122,10 +141,13 @@ def main(argv=None):
             buf.clearStaged()
             buf.push(items)
             buf.recordCopyToDevice()
-        deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
-        sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
-        debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423
-        debug_lines.recordDraw(None, 0, target, rect, cameras)  # renderer.cpp:425-427, :445-476 (only when enabled)
+        if pipeline == "compute-collection":  # renderer.cpp:431-438: the collection only
+            collection.recordDrawCommands(None, target, rect)
+        else:
+            deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
+            sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
+            debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423
+            debug_lines.recordDraw(None, 0, target, rect, cameras)  # renderer.cpp:425-427, :445-476 (only when enabled)
         pl.recordOETF(None, target, W, H)
         if present:  # editor.cpp:355-361: the whole scene onto the whole swapchain image, LINEAR
             pl.record_copy_image_to_image(None, target, swapchain, dstFormat=present[2])

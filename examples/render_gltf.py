@@ -4,6 +4,11 @@ whole path: shadow raster, G-buffer raster, lights, transmittance + sky-view LUT
 
     python examples/render_gltf.py [model.glb | model.gltf] --out /tmp/gltf.ppm [--embedded-images]
                                    [--present 1920x1080[:rgba8|bgra8|a2b10g10r10]]
+                                   [--pipeline compute-collection[:booleanpush|gradient_color|sparse_push_constant|matrix_color]]
+
+--pipeline compute-collection[:NAME] records the editor's other rendering pipeline (renderer.cpp:431-438,
+include/szg/compute_collection.h) over the scene colour instead of the deferred frame: one program of the collection
+(default gradient_color) with a visible block; the asset is still loaded and uploaded. The OETF and --present follow.
 
 --present ends the frame as the reference's editor does (editor.cpp:355-361, include/szg/present.h): the scene colour is
 blitted on the GPU, LINEAR, onto a swapchain-sized image of the given format, and --out is written from that image.
@@ -55,11 +60,18 @@ def main(argv=None):
     ap.add_argument("--embedded-images", action="store_true", help="also decode images stored in GLB buffer views (the reference does not)")
     ap.add_argument("--present", default="", metavar="WxH[:format]",
                     help="blit the frame onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) on the GPU and write --out from it")
+    ap.add_argument("--pipeline", default="deferred", metavar="deferred|compute-collection[:NAME]",
+                    help="the rendering pipeline of Renderer::recordDraw (renderer.cpp:379-439)")
     args = ap.parse_args(argv)
 
     import torch
 
     from syzygy_amd import abi, assets, lib, meshes, pipelines as pl, scene
+
+    try:
+        pipeline, shader = pl.parse_pipeline_option(args.pipeline)
+    except ValueError as e:
+        ap.error(f"--pipeline {e}")
 
     path = args.path
     if not path:
@@ -117,8 +129,14 @@ def main(argv=None):
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=1, max_shadow_maps=3, shadow_map_dim=2048)
     sky = pl.SkyViewComputePipeline.create()
     rect = pl.rect(W, H)
-    deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
-    sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
+    if pipeline == "compute-collection":  # renderer.cpp:431-438: the collection only
+        collection = pl.ComputeCollectionPipeline()
+        collection.selectShaderByName(shader)
+        collection.writeExampleValues()
+        collection.recordDrawCommands(None, target, rect)
+    else:
+        deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
+        sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     pl.recordOETF(None, target, W, H)
     try:
         present = pl.parse_present_option(args.present) if args.present else None  # (width, height, format)

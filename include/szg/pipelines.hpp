@@ -15,6 +15,7 @@
 //   DebugLineGraphicsPipeline   pipelines.hpp:238-268      szg::DebugLineGraphicsPipeline (szg/debuglines.h)
 //   recordCopyImageToImage      imageoperations.cpp:45-176 szg::recordCopyImageToImage (szg/present.h)
 //   Editor::endFrame's tail     editor.cpp:303-361         szg::recordPresent
+//   ComputeCollectionPipeline   pipelines.hpp:166-235      szg::ComputeCollectionPipeline (szg/compute_collection.h)
 //   std::span<MeshInstanced const> sceneGeometry           szg_fill_scene const* (synthetic)
 //
 // Error behaviour follows the reference: construction failures give an invalid object /
@@ -23,13 +24,16 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <span>
+#include <string_view>
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/compute_collection.h"
 #include "szg/debuglines.h"
 #include "szg/present.h"
 #include "szg/raster.h"
@@ -542,4 +546,103 @@ inline auto recordPresentEncoded(hipStream_t cmd, SceneTexture const& sceneTextu
     return recordCopyImageToImage(cmd, sceneTexture.color(), swapchainImage, sourceSubregion,
                                   szg_rect{0, 0, swapchainImage.width, swapchainImage.height}, encode);
 }
+
+// ---- compute-collection pipeline (szg/compute_collection.h) ----
+// The class the reference calls ComputeCollectionPipeline (renderer/pipelines.hpp:166-235, pipelines.cpp:223-368), with its
+// public names, over szg_record_compute_collection. Here the collection is a fixed table of four programs
+// (renderer.cpp:238-243) that the library describes, so an object is one array of {reflection, byte block} entries and a
+// cursor: there are no Vulkan handles, no shader paths and nothing to load, the constructor touches no device, and the
+// collection is never empty. Every block is zero-filled at construction and keeps its bytes while another program is
+// selected.
+struct ComputeCollectionPipeline
+{
+    // what the reference's ShaderReflectionData::PushConstant tells the editor about one program
+    using PushConstant = szg_cc_reflection;
+
+    ComputeCollectionPipeline()
+    {
+        for (uint32_t program = 0; program < SZG_COMPUTE_COLLECTION_SHADER_COUNT; program++)
+        {
+            // on failure the entry keeps a zero block size: its spans are empty and a record call is refused by the library
+            if (szg_compute_collection_reflect(program, &m_reflections[program]) != SZG_OK)
+            {
+                std::fprintf(stderr, "[szg] ComputeCollectionPipeline: %s\n", szg_last_error());
+                m_reflections[program] = PushConstant{};
+                m_valid = false;
+            }
+        }
+    }
+
+    [[nodiscard]] auto valid() const -> bool { return m_valid; }
+    [[nodiscard]] auto lastStatus() const -> int { return m_lastStatus; }
+
+    // The selected program over the top-left drawExtent of the scene colour (only the extent of the rectangle is used, as the
+    // reference passes sceneSubregion.extent). The library copies the bytes before it returns and replaces their first 16
+    // with offset (0, 0) and the extent (szg/compute_collection.h, RECORD).
+    void recordDrawCommands(hipStream_t cmd, SceneTexture& sceneTexture, szg_rect drawExtent) const
+    {
+        recordDrawCommands(cmd, sceneTexture.color(), drawExtent.width, drawExtent.height);
+    }
+    void recordDrawCommands(hipStream_t cmd, szg_image const& color, uint32_t width, uint32_t height) const
+    {
+        detail::note(szg_record_compute_collection(cmd, m_selected, m_blocks[m_selected].data(), blockBytes(), &color, width, height),
+                     "szg_record_compute_collection", m_lastStatus);
+    }
+
+    void cleanup() {} // nothing is owned on the device
+
+    // the selected program's block: editable in place / read-only
+    auto mapPushConstantBytes() -> std::span<uint8_t> { return {m_blocks[m_selected].data(), blockBytes()}; }
+    [[nodiscard]] auto readPushConstantBytes() const -> std::span<uint8_t const> { return {m_blocks[m_selected].data(), blockBytes()}; }
+
+    [[nodiscard]] auto currentShader() const -> PushConstant const& { return m_reflections[m_selected]; }
+
+    // An index outside the table is reported and ignored: the selection stays where it was.
+    void selectShader(size_t index)
+    {
+        if (index < m_reflections.size())
+        {
+            m_selected = static_cast<uint32_t>(index);
+            return;
+        }
+        std::fprintf(stderr, "[szg] ComputeCollectionPipeline::selectShader(%zu): the collection has %zu programs, selection unchanged\n",
+                     index, m_reflections.size());
+    }
+    [[nodiscard]] auto shaderIndex() const -> size_t { return m_selected; }
+    [[nodiscard]] auto shaderCount() const -> size_t { return m_reflections.size(); }
+    [[nodiscard]] auto shaders() const -> std::span<PushConstant const> { return m_reflections; }
+
+    // This library's addition: write `values` (floats; for a bool member 32-bit words, true = 1) into member `name` of the
+    // selected block, found in the reflection table. False when there is no such member or the count is not the member's.
+    template <typename T> auto writePushConstant(std::string_view name, std::span<T const> values) -> bool
+    {
+        static_assert(sizeof(T) == 4, "members are made of 32-bit components");
+        PushConstant const& reflection = currentShader();
+        for (uint32_t i = 0; i < reflection.member_count; i++)
+        {
+            szg_cc_member const& member = reflection.members[i];
+            if (name == member.name)
+            {
+                if (values.size_bytes() != member.size_bytes || member.offset_bytes + member.size_bytes > blockBytes())
+                {
+                    return false;
+                }
+                std::memcpy(m_blocks[m_selected].data() + member.offset_bytes, values.data(), member.size_bytes);
+                return true;
+            }
+        }
+        return false;
+    }
+
+  private:
+    using Block = std::array<uint8_t, SZG_COMPUTE_COLLECTION_MAX_BLOCK_BYTES>;
+    // bytes of the selected block that belong to its program (the arrays have the size of the largest block)
+    [[nodiscard]] auto blockBytes() const -> uint32_t { return m_reflections[m_selected].padded_size_bytes; }
+
+    std::array<PushConstant, SZG_COMPUTE_COLLECTION_SHADER_COUNT> m_reflections{};
+    std::array<Block, SZG_COMPUTE_COLLECTION_SHADER_COUNT> m_blocks{}; // zero-filled
+    uint32_t m_selected{0};
+    bool m_valid{true};
+    mutable int m_lastStatus{SZG_OK};
+};
 } // namespace szg

@@ -9,8 +9,9 @@
 //                         renderer/scene.cpp:95-574         calculateShadowBounds, shadowBounds, geometry, addMeshInstance,
 //                                                           addSpotlight, defaultScene, tick
 //   DebugLines            pipelines/debuglines.hpp:22-68    szg::DebugLines: enabled, lineWidth, vertices, push* builders
-//   Renderer::recordDraw  renderer/renderer.cpp:278-476     szg::Renderer::recordDraw (deferred pipeline branch, debug lines
-//                                                           included; the generic compute collection is an editor demo)
+//   Renderer::recordDraw  renderer/renderer.cpp:278-476     szg::Renderer::recordDraw (both branches: DEFERRED, debug lines
+//                                                           included, and COMPUTE_COLLECTION)
+//   RenderingPipelines    renderer/renderer.hpp             szg::RenderingPipelines, Renderer::setActiveRenderingPipeline
 //
 // Not mirrored: Scene::handleInput (window input), Scene::diagonalWaveScene (its instance rotations come from the
 // reference's random quaternion source and are not reproducible).
@@ -231,8 +232,15 @@ struct DebugLines
     void recordCopy(hipStream_t cmd) { vertices.recordCopyToDevice(cmd); }
 };
 
-// The part of Renderer (renderer.hpp / renderer.cpp:114-124, :278-443) that owns the staged parameter buffers and the two
-// pipelines and records one frame of the deferred + atmosphere path.
+// The editor's pipeline switch ("Deferred" / "Compute Collection", ui/engineui.cpp:19-22)
+enum class RenderingPipelines
+{
+    DEFERRED = 0,
+    COMPUTE_COLLECTION = 1,
+};
+
+// The part of Renderer (renderer.hpp / renderer.cpp:114-124, :234-247, :278-443) that owns the staged parameter buffers and
+// the pipelines and records one frame: the deferred + atmosphere path (the default) or the compute collection.
 struct Renderer
 {
     static auto create(uint32_t capacityWidth, uint32_t capacityHeight, uint32_t shadowMapDimension = 8192) -> std::optional<Renderer>
@@ -244,8 +252,10 @@ struct Renderer
         r.m_deferredShadingPipeline = std::make_unique<DeferredShadingPipeline>(capacityWidth, capacityHeight, 16, 10, shadowMapDimension);
         r.m_skyViewComputePipeline = SkyViewComputePipeline::create();
         r.m_debugLines = DebugLines::create(); // renderer.cpp:114-124, DEBUGLINES_CAPACITY (renderer.hpp:103)
+        r.m_genericComputePipeline = std::make_unique<ComputeCollectionPipeline>(); // renderer.cpp:234-247
         if (!r.m_camerasBuffer.valid() || !r.m_atmospheresBuffer.valid() || !r.m_directionalLightsBuffer.valid() ||
-            !r.m_deferredShadingPipeline->valid() || r.m_skyViewComputePipeline == nullptr || !r.m_debugLines.valid())
+            !r.m_deferredShadingPipeline->valid() || r.m_skyViewComputePipeline == nullptr || !r.m_debugLines.valid() ||
+            !r.m_genericComputePipeline->valid())
         {
             return std::nullopt;
         }
@@ -253,6 +263,9 @@ struct Renderer
     }
 
     void setRenderAtmosphere(bool render) { m_renderAtmosphere = render; }
+    // what imguiRenderingSelection(m_activeRenderingPipeline) edits (renderer.cpp:256)
+    void setActiveRenderingPipeline(RenderingPipelines pipeline) { m_activeRenderingPipeline = pipeline; }
+    [[nodiscard]] auto activeRenderingPipeline() const -> RenderingPipelines { return m_activeRenderingPipeline; }
 
     void recordDraw(hipStream_t cmd, Scene const& scene, SceneTexture& sceneTexture, szg_rect sceneSubregion)
     {
@@ -292,6 +305,13 @@ struct Renderer
                 }
             }
         }
+        if (m_activeRenderingPipeline == RenderingPipelines::COMPUTE_COLLECTION)
+        {
+            // renderer.cpp:431-438: the collection only, over the subregion's EXTENT; no shadow, G-buffer, light, atmosphere
+            // or debug-line launches
+            m_genericComputePipeline->recordDrawCommands(cmd, sceneTexture, sceneSubregion);
+            return;
+        }
         std::vector<SpotLightPacked> const none{};
         m_deferredShadingPipeline->recordDrawCommands(cmd, sceneSubregion, sceneTexture, m_renderAtmosphere ? 1u : 0u,
                                                       m_directionalLightsBuffer, scene.spotlightsRender ? scene.spotlights : none, 0,
@@ -323,6 +343,7 @@ struct Renderer
 
     [[nodiscard]] auto deferredShadingPipeline() -> DeferredShadingPipeline& { return *m_deferredShadingPipeline; }
     [[nodiscard]] auto debugLines() -> DebugLines& { return m_debugLines; }
+    [[nodiscard]] auto genericComputePipeline() -> ComputeCollectionPipeline& { return *m_genericComputePipeline; }
 
   private:
     bool m_renderAtmosphere{true};
@@ -332,5 +353,7 @@ struct Renderer
     std::unique_ptr<DeferredShadingPipeline> m_deferredShadingPipeline{};
     std::unique_ptr<SkyViewComputePipeline> m_skyViewComputePipeline{};
     DebugLines m_debugLines{};
+    std::unique_ptr<ComputeCollectionPipeline> m_genericComputePipeline{};
+    RenderingPipelines m_activeRenderingPipeline{RenderingPipelines::DEFERRED};
 };
 } // namespace szg

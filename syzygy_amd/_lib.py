@@ -54,6 +54,10 @@ def lib():
         except AttributeError as e:
             # additive entry points do not move the ABI version (include/szg/abi.h): an older build of the same version lacks them
             raise RuntimeError(f"{path} predates include/szg/present.h ({e}); rebuild the library") from e
+        try:
+            abi.bind(handle, abi.COMPUTE_COLLECTION_FUNCTIONS)
+        except AttributeError as e:
+            raise RuntimeError(f"{path} predates include/szg/compute_collection.h ({e}); rebuild the library") from e
         _LIB = handle
     return _LIB
 

@@ -550,6 +550,48 @@ PRESENT_FUNCTIONS = {
     "szg_record_present": (C.c_int, [VP, P(Image), P(Image), P(PresentInfo)]),
 }
 
+# include/szg/compute_collection.h
+SZG_COMPUTE_COLLECTION_SHADER_COUNT = 4
+SZG_COMPUTE_COLLECTION_MAX_EXTENT = 16384
+SZG_COMPUTE_COLLECTION_MAX_BLOCK_BYTES = 208
+SZG_COMPUTE_COLLECTION_PREFIX_BYTES = 16
+SZG_COMPUTE_COLLECTION_MAX_MEMBERS = 6
+SZG_COMPUTE_COLLECTION_WORKGROUP = 16
+SZG_CC_BOOLEANPUSH = 0
+SZG_CC_GRADIENT_COLOR = 1
+SZG_CC_SPARSE_PUSH_CONSTANT = 2
+SZG_CC_MATRIX_COLOR = 3
+SZG_CC_COMPONENT_FLOAT = 0
+SZG_CC_COMPONENT_BOOL = 1
+
+
+class CCMember(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("offset_bytes", U32), ("size_bytes", U32), ("padded_size_bytes", U32),
+                ("component_type", U32), ("vector_width", U32), ("column_count", U32)]
+
+
+class CCReflection(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("size_bytes", U32), ("padded_size_bytes", U32), ("layout_offset_bytes", U32),
+                ("local_size", U32 * 3), ("member_count", U32), ("members", CCMember * SZG_COMPUTE_COLLECTION_MAX_MEMBERS)]
+
+
+# The blocks the examples render with `--pipeline compute-collection[:NAME]` (member -> values in block order; a mat4 as its
+# 16 floats column by column): something visible, since the all-zero block of a new pipeline renders transparent black.
+COMPUTE_COLLECTION_EXAMPLE_VALUES = {
+    "booleanpush": {"row1": [1, 0, 1, 0], "row2": [0, 1, 0, 1], "row3": [1, 0, 1, 0], "row4": [0, 1, 0, 1]},
+    "gradient_color": {"topColor": [0.05, 0.10, 0.60, 1.0], "bottomColor": [1.0, 0.55, 0.10, 1.0]},
+    "sparse_push_constant": {"topRG": [0.9, 0.2], "topBA": [0.3, 1.0], "bottomRG": [0.1, 0.8], "bottomBA": [0.6, 1.0]},
+    "matrix_color": {"red": [c / 3.0 for c in range(4) for _ in range(4)],
+                     "green": [r / 3.0 for _ in range(4) for r in range(4)],
+                     "blue": [((r + c) % 2) * 0.75 for c in range(4) for r in range(4)]},
+}
+
+COMPUTE_COLLECTION_FUNCTIONS = {
+    "szg_compute_collection_shader_count": (U32, []),
+    "szg_compute_collection_reflect": (C.c_int, [U32, P(CCReflection)]),
+    "szg_record_compute_collection": (C.c_int, [VP, U32, VP, U32, P(Image), U32, U32]),
+}
+
 
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""

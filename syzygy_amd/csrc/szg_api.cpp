@@ -1518,6 +1518,107 @@ extern "C" int szg_record_present(void* stream, const szg_image* src, const szg_
     return SZG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Compute-collection pipeline (include/szg/compute_collection.h): renderer.cpp:431-438 -> pipelines.cpp:223-368
+// ---------------------------------------------------------------------------
+namespace
+{
+// What ShaderReflectionData::PushConstant holds for the four programs of renderer.cpp:238-243. Static tables; their truth is
+// checked against the reference's binaries by tests/test_compute_collection_reflection.py, not trusted.
+#define SZG_CC_PREFIX_MEMBERS                                                                                                  \
+    {"drawOffset", 0u, 8u, 8u, SZG_CC_COMPONENT_FLOAT, 2u, 1u}, { "drawExtent", 8u, 8u, 8u, SZG_CC_COMPONENT_FLOAT, 2u, 1u }
+const szg_cc_reflection g_ccReflection[SZG_COMPUTE_COLLECTION_SHADER_COUNT] = {
+    {"booleanpush", 80u, 80u, 0u, {16u, 16u, 1u}, 6u,
+     {SZG_CC_PREFIX_MEMBERS,
+      {"row1", 16u, 16u, 16u, SZG_CC_COMPONENT_BOOL, 4u, 1u},
+      {"row2", 32u, 16u, 16u, SZG_CC_COMPONENT_BOOL, 4u, 1u},
+      {"row3", 48u, 16u, 16u, SZG_CC_COMPONENT_BOOL, 4u, 1u},
+      {"row4", 64u, 16u, 16u, SZG_CC_COMPONENT_BOOL, 4u, 1u}}},
+    {"gradient_color", 48u, 48u, 0u, {16u, 16u, 1u}, 4u,
+     {SZG_CC_PREFIX_MEMBERS,
+      {"topColor", 16u, 16u, 16u, SZG_CC_COMPONENT_FLOAT, 4u, 1u},
+      {"bottomColor", 32u, 16u, 16u, SZG_CC_COMPONENT_FLOAT, 4u, 1u}}},
+    {"sparse_push_constant", 80u, 80u, 0u, {16u, 16u, 1u}, 6u,
+     {SZG_CC_PREFIX_MEMBERS,
+      {"topRG", 16u, 8u, 16u, SZG_CC_COMPONENT_FLOAT, 2u, 1u},
+      {"topBA", 32u, 8u, 16u, SZG_CC_COMPONENT_FLOAT, 2u, 1u},
+      {"bottomRG", 48u, 8u, 16u, SZG_CC_COMPONENT_FLOAT, 2u, 1u},
+      {"bottomBA", 64u, 8u, 16u, SZG_CC_COMPONENT_FLOAT, 2u, 1u}}},
+    {"matrix_color", 208u, 208u, 0u, {16u, 16u, 1u}, 5u,
+     {SZG_CC_PREFIX_MEMBERS,
+      {"red", 16u, 64u, 64u, SZG_CC_COMPONENT_FLOAT, 4u, 4u},
+      {"green", 80u, 64u, 64u, SZG_CC_COMPONENT_FLOAT, 4u, 4u},
+      {"blue", 144u, 64u, 64u, SZG_CC_COMPONENT_FLOAT, 4u, 4u}}},
+};
+#undef SZG_CC_PREFIX_MEMBERS
+} // namespace
+
+extern "C" uint32_t szg_compute_collection_shader_count(void) { return SZG_COMPUTE_COLLECTION_SHADER_COUNT; }
+
+extern "C" int szg_compute_collection_reflect(uint32_t index, szg_cc_reflection* out)
+{
+    if (out == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_compute_collection_reflect: out is NULL");
+    }
+    if (index >= SZG_COMPUTE_COLLECTION_SHADER_COUNT)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_compute_collection_reflect: shader index %u, the collection has %u programs", index,
+                    SZG_COMPUTE_COLLECTION_SHADER_COUNT);
+    }
+    *out = g_ccReflection[index];
+    return SZG_OK;
+}
+
+extern "C" int szg_record_compute_collection(void* stream, uint32_t shader_index, const void* push_constant_bytes, uint32_t byte_count,
+                                             const szg_image* color, uint32_t width, uint32_t height)
+{
+    // everything here runs on the host, before anything is launched
+    if (push_constant_bytes == nullptr || color == nullptr || color->data == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: push-constant bytes, colour image or its data is NULL");
+    }
+    if (shader_index >= SZG_COMPUTE_COLLECTION_SHADER_COUNT)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: shader index %u, the collection has %u programs", shader_index,
+                    SZG_COMPUTE_COLLECTION_SHADER_COUNT);
+    }
+    szg_cc_reflection const& program = g_ccReflection[shader_index];
+    if (byte_count != program.padded_size_bytes)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: %u bytes, the block of %s has %u", byte_count, program.name,
+                    program.padded_size_bytes);
+    }
+    if (color->format != SZG_FORMAT_RGBA16_UNORM)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: colour format %u, must be RGBA16_UNORM", color->format);
+    }
+    if (color->width > SZG_COMPUTE_COLLECTION_MAX_EXTENT || color->height > SZG_COMPUTE_COLLECTION_MAX_EXTENT)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: colour image %ux%u exceeds %u texels", color->width,
+                    color->height, SZG_COMPUTE_COLLECTION_MAX_EXTENT);
+    }
+    if ((size_t)color->pitch_bytes < (size_t)color->width * 8u || color->pitch_bytes % 8u != 0u ||
+        reinterpret_cast<uintptr_t>(color->data) % 8u != 0u)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: pitch %u / alignment invalid for %u texels of 8 bytes",
+                    color->pitch_bytes, color->width);
+    }
+    if (width == 0u || height == 0u || width > color->width || height > color->height)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: extent %ux%u is empty or leaves the %ux%u image", width,
+                    height, color->width, color->height);
+    }
+    // pipelines.cpp:319-344: a copy of the bytes, its first 16 overwritten with offset (0, 0) and the extent as floats
+    szg::CCBlock block{};
+    std::memcpy(block.w, push_constant_bytes, byte_count);
+    float const prefix[4] = {0.0f, 0.0f, static_cast<float>(width), static_cast<float>(height)};
+    static_assert(sizeof prefix == SZG_COMPUTE_COLLECTION_PREFIX_BYTES, "prefix layout");
+    std::memcpy(block.w, prefix, sizeof prefix);
+    SZG_HIP(szg::launch_compute_collection(static_cast<hipStream_t>(stream), shader_index, block, *color, width, height));
+    return SZG_OK;
+}
+
 extern "C" {
 
 int szg_compose_rowtiles(void* stream, const void* gathered, size_t tile_stride_bytes, uint32_t nranks, uint32_t block_rows,

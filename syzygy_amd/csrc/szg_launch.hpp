@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "szg/abi.h"
+#include "szg/compute_collection.h"
 #include "szg/debuglines.h"
 #include "szg/present.h"
 #include "szg/raster.h"
@@ -220,4 +221,16 @@ hipError_t launch_debug_lines(hipStream_t s, const szg_scene_texture& scene, uns
 // Arguments already validated; `table` is the OETF table of info.encode, or nullptr for SZG_PRESENT_ENCODE_NONE.
 hipError_t launch_present(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_present_info& info,
                           const unsigned short* table);
+
+// ---- compute-collection pipeline (kernels_compute_collection.hip, include/szg/compute_collection.h) ----
+// A push-constant block as the kernels take it, by value: the largest of the four (matrix_color), zero-filled behind the
+// bytes of a smaller one.
+struct alignas(16) CCBlock
+{
+    unsigned w[SZG_COMPUTE_COLLECTION_MAX_BLOCK_BYTES / 4u];
+};
+static_assert(sizeof(CCBlock) == SZG_COMPUTE_COLLECTION_MAX_BLOCK_BYTES, "CCBlock layout");
+// Arguments already validated; `block` carries drawOffset = 0 and drawExtent = (width, height) in its first 16 bytes.
+hipError_t launch_compute_collection(hipStream_t s, unsigned shaderIndex, const CCBlock& block, const szg_image& color, unsigned width,
+                                     unsigned height);
 } // namespace szg

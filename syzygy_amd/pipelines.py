@@ -9,6 +9,7 @@ Names, argument order and meaning follow the reference:
   DebugLines                renderer/pipelines/debuglines.hpp:22-68
   DebugLineGraphicsPipeline renderer/pipelines.hpp:238-268
   record_copy_image_to_image / record_present   renderer/imageoperations.cpp:45-176, editor/editor.cpp:303-361
+  ComputeCollectionPipeline renderer/pipelines.hpp:166-235, pipelines.cpp:223-368
 with `cmd` (VkCommandBuffer) replaced by a HIP stream handle and Vulkan images by
 linear device buffers. torch is used only to own device memory and streams.
 """
@@ -283,6 +284,126 @@ def record_present(cmd, sceneTexture, sourceSubregion, swapchainImage, gammaFunc
                                     int(gammaFunction)))
     info = abi.PresentInfo(_as_rect(sourceSubregion), abi.Rect(0, 0, dst.width, dst.height), abi.SZG_FILTER_LINEAR, encode)
     check(lib().szg_record_present(_stream_handle(cmd), C.byref(src), C.byref(dst), C.byref(info)))
+
+
+# ---------------------------------------------------------------------------
+# Compute-collection pipeline (include/szg/compute_collection.h)
+# ---------------------------------------------------------------------------
+CCMember = namedtuple("CCMember", "name offsetBytes sizeBytes paddedSizeBytes componentType vectorWidth columnCount")
+CCPushConstant = namedtuple("CCPushConstant", "name sizeBytes paddedSizeBytes layoutOffsetBytes localSize members")
+
+
+def compute_collection_reflection():
+    """The reflection tables of the library (szg_compute_collection_reflect), one CCPushConstant per program in the order
+    of renderer.cpp:238-243: what ShaderReflectionData::PushConstant gives the editor. Needs no device."""
+    out = []
+    for index in range(lib().szg_compute_collection_shader_count()):
+        r = abi.CCReflection()
+        check(lib().szg_compute_collection_reflect(index, C.byref(r)))
+        members = tuple(CCMember(m.name.decode(), m.offset_bytes, m.size_bytes, m.padded_size_bytes, m.component_type,
+                                 m.vector_width, m.column_count) for m in r.members[: r.member_count])
+        out.append(CCPushConstant(r.name.decode(), r.size_bytes, r.padded_size_bytes, r.layout_offset_bytes,
+                                  tuple(r.local_size), members))
+    return out
+
+
+def record_compute_collection(cmd, shaderIndex, pushConstantBytes, color, width, height):
+    """szg_record_compute_collection over a torch tensor: `color` is a SceneTexture or an int16 / uint16 tensor [h, w, 4]
+    whose rows may be padded (the pitch is the row stride). The bytes are copied before the call returns."""
+    tensor = color.color if isinstance(color, SceneTexture) else color
+    if tensor.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+        raise ValueError(f"the colour image must hold 16-bit codes, got {tensor.dtype}")
+    im = _strided_image(tensor, abi.SZG_FORMAT_RGBA16_UNORM, 4)
+    raw = bytes(pushConstantBytes)
+    check(lib().szg_record_compute_collection(_stream_handle(cmd), int(shaderIndex), raw, len(raw), C.byref(im), int(width),
+                                              int(height)))
+
+
+class ComputeCollectionPipeline:
+    """pipelines.hpp:166-235: "a generic compute pipeline driven entirely by a push constant". Holds one byte block per
+    program, zeros at first (pipelines.cpp:255-257), which survive a switch of program; recordDrawCommands copies the current
+    one, overwrites its first 16 bytes with the draw extent (pipelines.cpp:330-344) and dispatches. No device work here."""
+
+    def __init__(self):
+        self._reflection = compute_collection_reflection()
+        self._pushConstants = [bytearray(r.paddedSizeBytes) for r in self._reflection]
+        self._shaderIndex = 0
+
+    def recordDrawCommands(self, cmd, sceneTexture, drawExtent):
+        """pipelines.cpp:291-368. `drawExtent` is (width, height) or an abi.Rect (its extent is taken, as the reference takes
+        sceneSubregion.extent)."""
+        if isinstance(drawExtent, abi.Rect):
+            drawExtent = (drawExtent.width, drawExtent.height)
+        record_compute_collection(cmd, self._shaderIndex, self._pushConstants[self._shaderIndex], sceneTexture,
+                                  drawExtent[0], drawExtent[1])
+
+    def mapPushConstantBytes(self):
+        """The current program's block, writable in place (a bytearray)."""
+        return self._pushConstants[self._shaderIndex]
+
+    def readPushConstantBytes(self):
+        return bytes(self._pushConstants[self._shaderIndex])
+
+    def selectShader(self, index):
+        """An index outside the table is a warning and leaves the selection where it was (as the reference's selectShader does)."""
+        if not 0 <= int(index) < len(self._reflection):
+            import warnings
+
+            warnings.warn(f"selectShader({index}): the collection has {len(self._reflection)} programs, selection unchanged")
+            return
+        self._shaderIndex = int(index)
+
+    def selectShaderByName(self, name):
+        names = [r.name for r in self._reflection]
+        if name not in names:
+            raise ValueError(f"{name!r}: expected one of {names}")
+        self._shaderIndex = names.index(name)
+
+    def shaderIndex(self):
+        return self._shaderIndex
+
+    def shaderCount(self):
+        return len(self._reflection)
+
+    def shaders(self):
+        """The reflection of every program (ShaderObjectReflected::reflectionData)."""
+        return list(self._reflection)
+
+    def currentShader(self):
+        return self._reflection[self._shaderIndex]
+
+    def writePushConstant(self, name, values):
+        """Write `values` into member `name` of the current block: floats, or for a bool member 32-bit words (true = 1).
+        A mat4 takes its 16 floats column by column."""
+        member = next((m for m in self.currentShader().members if m.name == name), None)
+        if member is None:
+            raise KeyError(f"{self.currentShader().name} has no member {name!r}")
+        count = member.vectorWidth * member.columnCount
+        values = list(values)
+        if len(values) != count:
+            raise ValueError(f"{name}: {count} values expected, got {len(values)}")
+        dtype = np.uint32 if member.componentType == abi.SZG_CC_COMPONENT_BOOL else np.float32
+        raw = np.asarray(values, dtype=dtype).tobytes()
+        assert len(raw) == member.sizeBytes
+        self._pushConstants[self._shaderIndex][member.offsetBytes: member.offsetBytes + member.sizeBytes] = raw
+
+    def writeExampleValues(self):
+        """The visible block of abi.COMPUTE_COLLECTION_EXAMPLE_VALUES for the current program."""
+        for name, values in abi.COMPUTE_COLLECTION_EXAMPLE_VALUES[self.currentShader().name].items():
+            self.writePushConstant(name, values)
+
+    def cleanup(self):
+        pass
+
+
+def parse_pipeline_option(text):
+    """'deferred' or 'compute-collection[:NAME]' (the examples' --pipeline switch) -> (name, shader name or None)."""
+    kind, _, shader = text.partition(":")
+    if kind == "deferred" and not shader:
+        return "deferred", None
+    if kind == "compute-collection" and (not shader or shader in abi.COMPUTE_COLLECTION_EXAMPLE_VALUES):
+        return "compute-collection", shader or "gradient_color"
+    raise ValueError(f"{text!r}: expected deferred or compute-collection[:{'|'.join(abi.COMPUTE_COLLECTION_EXAMPLE_VALUES)}]")
 
 
 class DeferredShadingPipeline:

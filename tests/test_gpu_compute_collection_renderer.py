@@ -1,0 +1,62 @@
+"""GPU: szg::Renderer::recordDraw with the editor's pipeline switch (include/szg/scene.hpp), through a C++ caller compiled
+here with hipcc (tests/cpp/record_draw_compute_collection.cpp). With COMPUTE_COLLECTION the scene colour is the model's image
+of the current program (spill beyond the subregion included) and a poisoned G-buffer and depth image keep every byte; switched
+back to DEFERRED the frame equals the frame of a renderer that never switched; selectShader(7) changes nothing."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from syzygy_amd import abi, lib
+from tests import compute_collection_model as model
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
+    lib()  # built and loadable
+    out = str(tmp_path_factory.mktemp("cpp") / "record_draw_compute_collection")
+    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(HERE, "cpp", "record_draw_compute_collection.cpp"), "-o", out, "-L" + csrc, "-lszg_hip",
+                    "-Wl,-rpath," + csrc], check=True)
+    return out
+
+
+@pytest.mark.parametrize("extent,texture", [((320, 180), (320, 180)), ((500, 300), (640, 360))], ids=["whole", "subregion"])
+def test_renderer_switches_between_deferred_and_the_collection(exe, tmp_path, extent, texture):
+    (W, H), (TW, TH) = extent, texture
+    prefix = str(tmp_path / "frame")
+    blocks = [model.pack_block(s, abi.COMPUTE_COLLECTION_EXAMPLE_VALUES[s], fill=0x3C) for s in model.SHADERS]
+    with open(prefix + ".blocks.bin", "wb") as f:
+        f.write(b"".join(blocks))
+    r = subprocess.run([exe, prefix, str(W), str(H), str(TW), str(TH)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    read = lambda s: np.fromfile(prefix + s, dtype=np.uint16).reshape(TH, TW, 4)  # noqa: E731
+    assert "default pipeline 0" in r.stdout and "shaders 4" in r.stdout  # DEFERRED unless switched
+    before = np.full((TH, TW, 4), 0xC3C3, np.uint16)  # what the caller filled the colour with
+    for index, (shader, block) in enumerate(zip(model.SHADERS, blocks)):
+        # the blocks of a new pipeline are zeros (pipelines.cpp:255-257)
+        assert f"shader {index} {shader} bytes {len(block)} zeros 1" in r.stdout
+        want, _ = model.render(shader, block, before, W, H)
+        got = read(f".cc{index}.bin")
+        bad = np.argwhere((got != want).any(axis=-1))
+        assert len(bad) == 0, f"{shader}: {len(bad)} texels differ, first {bad[:5].tolist()}"
+        before = want  # the next program writes over this one; texels outside the written set stay
+    # no shadow, G-buffer, light, atmosphere or debug-line launch; the instances' boxes were staged (renderer.cpp:355-365)
+    assert "gbuffer and depth untouched 1 status 0 lines staged 96 drawn 0" in r.stdout, r.stdout
+    assert "after selectShader(7) index 3" in r.stdout
+    assert np.array_equal(read(".cc7.bin"), read(".cc3.bin"))
+    assert "writePushConstant 1" in r.stdout
+    reference, back = read(".reference.bin"), read(".back.bin")
+    assert np.array_equal(back[:H, :W], reference[:H, :W]), "the deferred frame after the switch differs"
+    assert reference[:H, :W].any() and not np.array_equal(back[:H, :W], read(".cc3.bin")[:H, :W])
+    assert np.array_equal(back[H:], read(".cc3.bin")[H:]) and np.array_equal(back[:, W:], read(".cc3.bin")[:, W:])
