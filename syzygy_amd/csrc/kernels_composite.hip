@@ -156,8 +156,11 @@ SZG_DEV V3 sampleAerial(const AerialLut& A, float sx, float sy, float dist)
     return (l0 * (1.0f - wz) + l1 * wz) * ramp;
 }
 
+#ifndef SZG_COMPOSITE_WAVES
+#define SZG_COMPOSITE_WAVES 4
+#endif
 template <bool FAST>
-__global__ __launch_bounds__(256, 3) void k_composite(szg_image color, szg_image depth, szg_image debug, GBufferPtrsC g,
+__global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_image color, szg_image depth, szg_image debug, GBufferPtrsC g,
                                                    unsigned drawW, unsigned drawH, unsigned localRows, RowMap rm,
                                                    ShadowSlot sunSlot, const szg_atmosphere_packed* __restrict__ atmospheres,
                                                    unsigned atmosphereIndex, const szg_camera_packed* __restrict__ cameras,
@@ -377,10 +380,14 @@ __global__ __launch_bounds__(256, 3) void k_composite(szg_image color, szg_image
     }
 
     // ---- phase B ---------------------------------------------------------
-    // The march needs ~125 VGPRs by itself; what phase C wants back (12 floats) is parked in LDS meanwhile so
-    // that the kernel fits 168 VGPRs = 3 waves per SIMD instead of 2 (LDS is otherwise unused here; [k][tid]
-    // indexing is conflict-free).
+    // The march needs ~125 VGPRs by itself. Everything per-pixel that phase C wants back (12 floats), the two march
+    // requests (origin, direction, length), their results and the three flags wait in LDS meanwhile - a queue of two slots
+    // per thread - so that nothing of phases A and C is live across the march (LDS is otherwise unused here; every thread
+    // touches only its own [k][tid] slots: conflict-free, no barrier, and the early return above stays legal).
     __shared__ float s_park[12][256];
+    __shared__ float s_request[2][7][256];
+    __shared__ float s_result[2][3][256];
+    __shared__ unsigned s_flags[256];
     {
         float const park[12] = {base.x, base.y, base.z, coef.x, coef.y, coef.z, env2.x, env2.y, env2.z,
                                 surfaceLuminance.x, surfaceLuminance.y, surfaceLuminance.z};
@@ -389,29 +396,49 @@ __global__ __launch_bounds__(256, 3) void k_composite(szg_image color, szg_image
         {
             s_park[k][tid] = park[k];
         }
-    }
-    V3 ap0 = splat(0.0f), ap1 = splat(0.0f);
-#pragma unroll 1
-    for (int k = 0; k < 2; k++)
-    {
-        bool const active = (k == 0) ? march0 : march1;
-        if (active)
+        float const request[2][7] = {{o0.x, o0.y, o0.z, d0.x, d0.y, d0.z, l0}, {o1.x, o1.y, o1.z, d1.x, d1.y, d1.z, l1}};
+#pragma unroll
+        for (int k = 0; k < 2; k++)
         {
-            V3 const o = (k == 0) ? o0 : o1;
-            V3 const d = (k == 0) ? d0 : d1;
-            float const l = (k == 0) ? l0 : l1;
-            V3 const r = scatteringIntegral(L, a, o, d, l);
-            if (k == 0)
+#pragma unroll
+            for (int c = 0; c < 7; c++)
             {
-                ap0 = r;
-            }
-            else
-            {
-                ap1 = r;
+                s_request[k][c][tid] = request[k][c];
             }
         }
+        s_flags[tid] = (march0 ? 1u : 0u) | (march1 ? 2u : 0u) | (hasReflection ? 4u : 0u);
     }
+    // (the compiler must not forward the stores above to the loads below: the values would stay in registers)
+    asm volatile("" ::: "memory");
+    // The frame's constants move from the scalar block to vector registers again (load_atm: ~45 moves per wave), so that
+    // phase A's copies die with phase A instead of being spilled around the march.
+    Atm const aB = load_atm(*prep);
+#ifdef SZG_EXP_LDS_TLUT
+    TLut const& LB = L;
+#else
+    TLut const LB = make_tlut(tlut, tW, tH, *prep);
+#endif
+#pragma unroll 1
+    for (unsigned k = 0; k < 2u; k++)
+    {
+        if (((s_flags[tid] >> k) & 1u) != 0u)
+        {
+            V3 const o = mk3(s_request[k][0][tid], s_request[k][1][tid], s_request[k][2][tid]);
+            V3 const d = mk3(s_request[k][3][tid], s_request[k][4][tid], s_request[k][5][tid]);
+            V3 const r = scatteringIntegral(LB, aB, o, d, s_request[k][6][tid]);
+            s_result[k][0][tid] = r.x;
+            s_result[k][1][tid] = r.y;
+            s_result[k][2][tid] = r.z;
+        }
+    }
+    asm volatile("" ::: "memory");
 
+    unsigned const flags = s_flags[tid];
+    march0 = (flags & 1u) != 0u;
+    march1 = (flags & 2u) != 0u;
+    hasReflection = (flags & 4u) != 0u;
+    V3 const ap0 = march0 ? mk3(s_result[0][0][tid], s_result[0][1][tid], s_result[0][2][tid]) : splat(0.0f);
+    V3 const ap1 = march1 ? mk3(s_result[1][0][tid], s_result[1][1][tid], s_result[1][2][tid]) : splat(0.0f);
     base = mk3(s_park[0][tid], s_park[1][tid], s_park[2][tid]);
     coef = mk3(s_park[3][tid], s_park[4][tid], s_park[5][tid]);
     env2 = mk3(s_park[6][tid], s_park[7][tid], s_park[8][tid]);
@@ -425,7 +452,8 @@ __global__ __launch_bounds__(256, 3) void k_composite(szg_image color, szg_image
         V3 const e2 = march1 ? (env2 + ap1) : env2;
         transfer = transfer + coef * e2;
     }
-    V3 const luminance = transfer * a.sunIntensitySpectrum;
+    // (read again from the frame block, scalar loads, instead of holding three registers across the march)
+    V3 const luminance = transfer * mk3(prep->a.sunIntensitySpectrum.x, prep->a.sunIntensitySpectrum.y, prep->a.sunIntensitySpectrum.z);
     V3 const pre = luminance * 10.0f + surfaceLuminance;
     V3 const out = mk3(szg_powf(pre.x, 1.2f), szg_powf(pre.y, 1.2f), szg_powf(pre.z, 1.2f));
     row_ptr<uint2>(color, y)[x] = pack_unorm16x4(out.x, out.y, out.z, 1.0f);

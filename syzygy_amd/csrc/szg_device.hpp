@@ -449,6 +449,11 @@ struct Atm
     // of zero-length segments rely on it), and (b) both densities exp(-altitude / H) have arguments in [-85, 80], where the
     // clamp of exp's argument is the identity.
     float innerCeil2;
+    // Frame-uniform operands of the march setup (scatteringIntegral), formed here - once per frame where the block comes from
+    // k_frame_prep - with the functions the setup used to call on the same inputs: szg_sinf / szg_cosf(sunAngularRadius),
+    // dotA(sun, sun), and its square root by the generic operator (lengthA) and by the lean one (sqrtP; meaningful when
+    // leanLength2(sun2) holds, which is the only case the lean setup reads it in).
+    float sinSunRadius, cosSunRadius, sun2, sunLength, sunLengthLean;
 };
 SZG_DEV bool plusZero3(V3 v)
 {
@@ -530,6 +535,11 @@ SZG_DEV Atm load_atm(const szg_atmosphere_packed* p)
     a.rcpDsR = rcpN(a.lean ? a.densityScaleRayleigh : 1.0f);
     a.rcpDsM = rcpN(a.lean ? a.densityScaleMie : 1.0f);
     a.rcp15 = rcpN(15.0f);
+    a.sinSunRadius = szg_sinf(a.sunAngularRadius);
+    a.cosSunRadius = szg_cosf(a.sunAngularRadius);
+    a.sun2 = dotA(a.incidentDirectionSun, a.incidentDirectionSun);
+    a.sunLength = lengthA(a.incidentDirectionSun);
+    a.sunLengthLean = sqrtP(a.sun2);
     return a;
 }
 
@@ -1159,7 +1169,7 @@ SZG_DEV V3 scatteringIntegral(const TLut& L, const Atm& a, V3 origin, V3 directi
     // The per-ray setup with the lean exact operators (same values) when the whole wave's origins lie above the lean floor
     // and the direction and sun vectors have ordinary lengths; otherwise hipcc's generic sqrtf / division.
     float const origin2 = dotA(origin, origin), direction2 = dotA(direction, direction);
-    float const sun2 = dotA(a.incidentDirectionSun, a.incidentDirectionSun);
+    float const sun2 = a.sun2;
     bool const setupLean = waveAll(a.lean && leanRadius2(a, origin2) && leanLength2(direction2) && leanLength2(sun2));
     float radius, mu, mu_sun;
     V3 const toSun = -a.incidentDirectionSun;
@@ -1169,21 +1179,21 @@ SZG_DEV V3 scatteringIntegral(const TLut& L, const Atm& a, V3 origin, V3 directi
         m.scatteringDir = -(direction * divN0(1.0f, lenDirection));
         radius = sqrtP(origin2);
         mu = divN0(dotA(origin, direction), radius * lenDirection);
-        mu_sun = divN0(dotA(origin, toSun), radius * sqrtP(sun2));
+        mu_sun = divN0(dotA(origin, toSun), radius * a.sunLengthLean);
     }
     else
     {
         m.scatteringDir = -normalizeA(direction);
         radius = lengthA(origin);
         mu = dotA(origin, direction) / (lengthA(origin) * lengthA(direction));
-        mu_sun = dotA(origin, toSun) / (lengthA(origin) * lengthA(a.incidentDirectionSun));
+        mu_sun = dotA(origin, toSun) / (lengthA(origin) * a.sunLength);
     }
 
     float const incidentCosine = dotA(a.incidentDirectionSun, m.scatteringDir);
     m.pR = phaseRayleigh(incidentCosine);
     m.pM = phaseMie(incidentCosine, 0.8f);
-    m.sin_sunRadius = szg_sinf(a.sunAngularRadius);
-    m.cos_sunRadius = szg_cosf(a.sunAngularRadius);
+    m.sin_sunRadius = a.sinSunRadius;
+    m.cos_sunRadius = a.cosSunRadius;
 
     // stepRadiusMu invariants (common.glinl:325)
     m.mu_sunAndStep = safeSqrt(mu_sun * mu - safeSqrt((1.0f - mu_sun * mu_sun) * (1.0f - mu * mu)));
