@@ -23,13 +23,25 @@
  *                (Olano & Greer 1997), which is what clipping + rasterising the pieces computes. A fragment
  *                exists only where 0 <= z_clip <= w_clip (Vulkan's depth clip volume).
  *   coverage     pixel centre (x + .5, y + .5). With h = ((x_c + w_c) * W/2, (y_c + w_c) * H/2, w_c) per vertex,
- *                edge function E_i = cross(h_j, h_k) . (px, py, 1) for (i, j, k) cyclic. A pixel is covered
- *                when s*E_i > 0 for the three edges, s = sign of det(h_0, h_1, h_2); a pixel centre exactly on
- *                an edge belongs to the triangle whose edge is a left edge (s*a_i > 0) or a top edge
- *                (a_i == 0 and s*b_i > 0) — the top-left rule. Two triangles that share an edge get exactly
- *                negated coefficients, so the raster is watertight and never double-hits.
- *   facing       det > 0 is clockwise in framebuffer space = front-facing (deferred.cpp:380).
- *   depth        z = (sum E_i z_i) / (sum E_i w_i); attributes = (sum E_i a_i) / (sum E_i) (perspective correct).
+ *                (two fp32 operations each: the sum, then the product with W/2 or H/2), the
+ *                edge function E_i = cross(h_j, h_k) . (px, py, 1) = det[h_j; h_k; (px, py, 1)] for (i, j, k) cyclic. A
+ *                pixel is covered when s*E_i > 0 for the three edges, s = sign of det(h_0, h_1, h_2); a pixel centre
+ *                exactly on an edge belongs to the triangle whose edge is a left edge (s*a_i > 0) or a top edge
+ *                (a_i == 0 and s*b_i > 0) — the top-left rule. The SIGNS of E_i, a_i, b_i and of det are those of the
+ *                exact values, as rational numbers, of these expressions in the fp32 h: the fp32 evaluation
+ *                e_i = (a_i px + b_i py) + c_i decides only where |e_i| exceeds its rounding budget
+ *                2^-21 (A (W + 1) + B (H + 1) + C) (A, B, C the sums of the magnitudes of the products a_i, b_i, c_i are
+ *                made of), elsewhere the sign is computed exactly (szg/exact_sign.h). The h values belong to the vertex,
+ *                so every triangle that meets at a vertex or along an edge sees the same lines: the exact rule
+ *                partitions the plane, and a closed mesh is rasterised watertight with no pixel hit twice — also at
+ *                pixel centres that are vertices, where fp32 signs of the edges of different triangles contradict
+ *                each other once c_i = hx_j hy_k - hx_k hy_j no longer fits in 24 bits (exactly negated coefficients
+ *                make a shared EDGE consistent, not the edges that meet at a vertex).
+ *   facing       det > 0 is clockwise in framebuffer space = front-facing (deferred.cpp:380); exact sign.
+ *   depth        with the fp32 e_i: z = (sum e_i z_i) / (sum e_i w_i), a fragment exists where 0 <= sum e_i z_i <= sum e_i w_i;
+ *                attributes = sum (e_i / S) a_i with S = (e_0 + e_1) + e_2: each weight is divided first, then the three
+ *                products are summed left to right (perspective correct; equal to (sum e_i a_i) / (sum e_i) up to rounding).
+ *                Where the exact rule accepts a pixel whose fp32 e_i is zero or slightly negative, that e_i is used as it is.
  *   order        primitives are numbered in submission order (mesh, surface, instance, triangle:
  *                vkCmdDrawIndexed with instanceCount, deferred.cpp:691-698); with GREATER the earliest
  *                primitive wins a depth tie.

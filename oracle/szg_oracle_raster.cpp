@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/exact_sign.h"
 #include "szg/fpmath.h"
 #include "szg/raster.h"
 
@@ -102,6 +103,10 @@ struct Primitive
 {
     float a[3], b[3], c[3];
     float z[3], w[3];
+    // raster.h "coverage": the sign of an edge function inside its rounding budget `noise` is the exact determinant's
+    float hx[3], hy[3]; // (hw is w)
+    float noise[3];     // < 0: not finite, the fp32 sign stands
+    float facing;       // +1 front, -1 back: the factor the coefficients carry
     // vertex-stage outputs of offscreen.vert for the fragment stage
     vec3 world[3];
     vec3 normal[3];
@@ -146,7 +151,16 @@ bool assemble(const vec4 clip[3], float W, float H, bool cullFront, Primitive& o
         out.b[i] = hx[k] * hw[j] - hx[j] * hw[k];
         out.c[i] = hx[j] * hy[k] - hx[k] * hy[j];
     }
-    float const det = (hx[0] * out.a[0] + hy[0] * out.b[0]) + hw[0] * out.c[0];
+    float det = (hx[0] * out.a[0] + hy[0] * out.b[0]) + hw[0] * out.c[0];
+    bool finite = true;
+    for (int i = 0; i < 3; i++)
+    {
+        finite = finite && fabsf(hx[i]) < INFINITY && fabsf(hy[i]) < INFINITY && fabsf(hw[i]) < INFINITY;
+    }
+    if (finite)
+    {
+        det = (float)szg_facing_sign(hx, hy, hw); // raster.h "facing": the exact determinant's sign
+    }
     if (!(det > 0.0f) && !(det < 0.0f))
     {
         return false; // degenerate or NaN
@@ -155,6 +169,21 @@ bool assemble(const vec4 clip[3], float W, float H, bool cullFront, Primitive& o
     if (cullFront ? front : !front)
     {
         return false;
+    }
+    out.facing = front ? 1.0f : -1.0f;
+    for (int i = 0; i < 3; i++)
+    {
+        // |error of e_i| <= 5 * 2^-24 (A px + B py + C): two roundings in each coefficient, three in the evaluation, A, B, C
+        // the sums of the magnitudes of the products; + 2^-120 for results that round in the denormal range. Bounded over
+        // the viewport and rounded up to 2^-21.
+        int const j = (i + 1) % 3, k = (i + 2) % 3;
+        float const A = fabsf(hy[j] * hw[k]) + fabsf(hy[k] * hw[j]);
+        float const B = fabsf(hx[k] * hw[j]) + fabsf(hx[j] * hw[k]);
+        float const Cc = fabsf(hx[j] * hy[k]) + fabsf(hx[k] * hy[j]);
+        float const noise = 0x1p-21f * ((A * (W + 1.0f) + B * (H + 1.0f)) + Cc) + 0x1p-120f;
+        out.noise[i] = (finite && noise < INFINITY) ? noise : -1.0f;
+        out.hx[i] = hx[i];
+        out.hy[i] = hy[i];
     }
     if (!front)
     {
@@ -175,11 +204,25 @@ inline void edges(const Primitive& t, float px, float py, float e[3])
         e[i] = (t.a[i] * px + t.b[i] * py) + t.c[i];
     }
 }
-inline bool covers(const Primitive& t, const float e[3])
+inline bool covers(const Primitive& t, const float e[3], float px, float py)
 {
     for (int i = 0; i < 3; i++)
     {
-        bool const in = e[i] > 0.0f || (e[i] == 0.0f && (t.a[i] > 0.0f || (t.a[i] == 0.0f && t.b[i] > 0.0f)));
+        bool in;
+        if (fabsf(e[i]) <= t.noise[i])
+        {
+            // inside the rounding budget: the exact sign of det[h_j; h_k; (px, py, 1)], and of a_i, b_i on a tie
+            int const j = (i + 1) % 3, k = (i + 2) % 3;
+            int const f = t.facing > 0.0f ? 1 : -1;
+            int const se = f * szg_edge_sign(t.hx[j], t.hy[j], t.w[j], t.hx[k], t.hy[k], t.w[k], px, py, (double)t.noise[i] * 0x1p-29);
+            int const sa = f * szg_diff_of_products_sign(t.hy[j], t.w[k], t.hy[k], t.w[j]);
+            int const sb = f * szg_diff_of_products_sign(t.hx[k], t.w[j], t.hx[j], t.w[k]);
+            in = se > 0 || (se == 0 && (sa > 0 || (sa == 0 && sb > 0)));
+        }
+        else
+        {
+            in = e[i] > 0.0f || (e[i] == 0.0f && (t.a[i] > 0.0f || (t.a[i] == 0.0f && t.b[i] > 0.0f)));
+        }
         if (!in)
         {
             return false;
@@ -430,7 +473,7 @@ void oracle_gbuffer_raster(const szg_scene_texture* scene, szg_rect drawRect, co
                     float e[3];
                     edges(t, px, py, e);
                     float depth;
-                    if (covers(t, e) && fragmentDepth(t, e, depth) && depth > best)
+                    if (covers(t, e, px, py) && fragmentDepth(t, e, depth) && depth > best)
                     {
                         best = depth;
                         winner = &t;
@@ -545,7 +588,7 @@ void oracle_shadow_raster(const szg_image* map, const szg_mat4* projView, float 
                     float e[3];
                     edges(t, px, py, e);
                     float depth;
-                    if (!covers(t, e) || !fragmentDepth(t, e, depth))
+                    if (!covers(t, e, px, py) || !fragmentDepth(t, e, depth))
                     {
                         continue;
                     }

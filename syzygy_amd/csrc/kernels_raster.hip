@@ -14,6 +14,7 @@
 //                    are written once: 52 B/px, coalesced
 //   k_shadow_tile    the same walk, depth only (front faces culled, GREATER_OR_EQUAL, depth bias)
 
+#include "szg/exact_sign.h"
 #include "szg_device.hpp"
 #include "szg_launch.hpp"
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(64) void k_raster_setup(const RasterDraw* __restric
         r.draw = di;
         r.instance = instance;
         r.tri = tri;
-        r.pad[0] = r.pad[1] = 0u;
+        r.facing = 0.0f;
         bool valid = i0 < d.vertexCount && i1 < d.vertexCount && i2 < d.vertexCount;
         if (valid)
         {
@@ -193,10 +194,37 @@ __global__ __launch_bounds__(64) void k_raster_setup(const RasterDraw* __restric
                 r.b[i] = hx[k] * hw[j] - hx[j] * hw[k];
                 r.c[i] = hx[j] * hy[k] - hx[k] * hy[j];
             }
-            float const det = (hx[0] * r.a[0] + hy[0] * r.b[0]) + hw[0] * r.c[0];
+            float det = (hx[0] * r.a[0] + hy[0] * r.b[0]) + hw[0] * r.c[0];
+            bool finite = true;
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+            {
+                finite = finite && fabsf(hx[i]) < INFINITY && fabsf(hy[i]) < INFINITY && fabsf(hw[i]) < INFINITY;
+            }
+            if (finite)
+            {
+                det = (float)szg_facing_sign(hx, hy, hw); // raster.h "facing": the exact determinant's sign
+            }
             valid = valid && (det > 0.0f || det < 0.0f);
             bool const front = det > 0.0f;
             valid = valid && (SHADOW ? !front : front); // shadow pass culls FRONT faces, G-buffer pass BACK faces
+            r.facing = front ? 1.0f : -1.0f;
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+            {
+                // the budget inside which the tile kernels take an edge function's sign exactly (raster.h "coverage"):
+                // |error of e_i| <= 5 * 2^-24 (A px + B py + C), two roundings in each coefficient and three in the
+                // evaluation, A, B, C the sums of the magnitudes of the products; + 2^-120 for results that round in the
+                // denormal range. Bounded over the viewport and rounded up to 2^-21.
+                int const j = (i + 1) % 3, k = (i + 2) % 3;
+                float const A = fabsf(hy[j] * hw[k]) + fabsf(hy[k] * hw[j]);
+                float const B = fabsf(hx[k] * hw[j]) + fabsf(hx[j] * hw[k]);
+                float const Cc = fabsf(hx[j] * hy[k]) + fabsf(hx[k] * hy[j]);
+                float const noise = 0x1p-21f * ((A * ((float)W + 1.0f) + B * ((float)H + 1.0f)) + Cc) + 0x1p-120f;
+                r.noise[i] = (finite && noise < INFINITY) ? noise : -1.0f; // < 0: the fp32 sign stands
+                r.hx[i] = hx[i];
+                r.hy[i] = hy[i];
+            }
             if (!front)
             {
 #pragma unroll
@@ -209,10 +237,9 @@ __global__ __launch_bounds__(64) void k_raster_setup(const RasterDraw* __restric
             }
             if (valid)
             {
-                // Conservative pixel box when every vertex is in front of the eye, else the viewport. Coverage is DEFINED by
-                // the fp32 edge functions (raster.h), and |error of e_i| <= noise_i = 2^-22 (A px + B py + C) with A, B, C the sums
-                // of the magnitudes of the products a_i, b_i, c_i are made of (two roundings each, three more in the
-                // evaluation). Every pixel the fp32 test can accept therefore lies in {e_i > -noise_i for all i}: the
+                // Conservative pixel box when every vertex is in front of the eye, else the viewport. Coverage is the sign
+                // of the exact edge functions (raster.h), and the fp32 e_i differ from them by at most noise_i (above).
+                // Every accepted pixel therefore lies in {e_i > -noise_i for all i}: the
                 // triangle T' bounded by the three edge lines pushed out by their noise. The box is the bounding box of T'
                 // (+- 1 px for its own rounding): the projected triangle itself for ordinary primitives, a few pixels more
                 // for distant tiny ones, and — because nearly parallel lines meet far away — the whole viewport where the
@@ -230,7 +257,7 @@ __global__ __launch_bounds__(64) void k_raster_setup(const RasterDraw* __restric
                         float const A = fabsf(hy[j] * hw[k]) + fabsf(hy[k] * hw[j]);
                         float const B = fabsf(hx[k] * hw[j]) + fabsf(hx[j] * hw[k]);
                         float const Cc = fabsf(hx[j] * hy[k]) + fabsf(hx[k] * hy[j]);
-                        pushed[i] = r.c[i] + 0x1p-22f * ((A * ((float)W + 1.0f) + B * ((float)H + 1.0f)) + Cc);
+                        pushed[i] = r.c[i] + (0x1p-21f * ((A * ((float)W + 1.0f) + B * ((float)H + 1.0f)) + Cc) + 0x1p-120f);
                     }
                     float x[3], y[3];
                     bool defined = true;
@@ -353,14 +380,27 @@ SZG_DEV void edgeFunctions(const PrimRec* __restrict__ t, float px, float py, fl
         e[i] = (t->a[i] * px + t->b[i] * py) + t->c[i];
     }
 }
-SZG_DEV bool coversPixel(const PrimRec* __restrict__ t, const float e[3])
+SZG_DEV bool coversPixel(const PrimRec* __restrict__ t, const float e[3], float px, float py)
 {
     bool in = true;
 #pragma unroll
     for (int i = 0; i < 3; i++)
     {
-        // top-left rule for a centre exactly on the edge (raster.h)
-        in = in && (e[i] > 0.0f || (e[i] == 0.0f && (t->a[i] > 0.0f || (t->a[i] == 0.0f && t->b[i] > 0.0f))));
+        if (fabsf(e[i]) <= t->noise[i])
+        {
+            // inside the rounding budget (rare): the exact sign of det[h_j; h_k; (px, py, 1)], and of a_i, b_i on a tie
+            int const j = (i + 1) % 3, k = (i + 2) % 3;
+            int const f = t->facing > 0.0f ? 1 : -1;
+            int const se = f * szg_edge_sign(t->hx[j], t->hy[j], t->w[j], t->hx[k], t->hy[k], t->w[k], px, py, (double)t->noise[i] * 0x1p-29);
+            int const sa = f * szg_diff_of_products_sign(t->hy[j], t->w[k], t->hy[k], t->w[j]);
+            int const sb = f * szg_diff_of_products_sign(t->hx[k], t->w[j], t->hx[j], t->w[k]);
+            in = in && (se > 0 || (se == 0 && (sa > 0 || (sa == 0 && sb > 0))));
+        }
+        else
+        {
+            // top-left rule for a centre exactly on the edge (raster.h)
+            in = in && (e[i] > 0.0f || (e[i] == 0.0f && (t->a[i] > 0.0f || (t->a[i] == 0.0f && t->b[i] > 0.0f))));
+        }
     }
     return in;
 }
@@ -553,7 +593,7 @@ __global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image 
         bool const ok = fragmentDepth(t, e, d);
         // GREATER in submission order: the walk order is arbitrary, so an equal depth goes to the earlier primitive — among
         // fragments; a depth equal to the clear value (0, also as an underflow of a huge primitive) is not GREATER than it
-        if (coversPixel(t, e) && ok && (d > best || (d == best && winner != 0xFFFFFFFFu && p < winner)))
+        if (coversPixel(t, e, px, py) && ok && (d > best || (d == best && winner != 0xFFFFFFFFu && p < winner)))
         {
             best = d;
             winner = p;
@@ -630,7 +670,7 @@ __global__ __launch_bounds__(256) void k_shadow_tile(const ShadowGen* __restrict
         float e[3];
         edgeFunctions(t, px, py, e);
         float d;
-        bool const ok = fragmentDepth(t, e, d) && coversPixel(t, e);
+        bool const ok = fragmentDepth(t, e, d) && coversPixel(t, e, px, py);
         if (biased)
         {
             // Vulkan depth bias o = m * slope + r * constant (raster.h / oracle_shadow_raster)

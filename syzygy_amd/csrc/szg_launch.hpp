@@ -151,9 +151,11 @@ struct PrimRec
     float a[3], b[3], c[3];
     float z[3], w[3];
     uint32_t draw, instance, tri;
-    uint32_t pad[2];
+    // where |e_i| <= noise[i] the sign comes from the exact determinant of the h values (hw is w); noise < 0: never
+    float hx[3], hy[3], noise[3];
+    float facing; // +1 front, -1 back: the factor a, b, c carry
 };
-static_assert(sizeof(PrimRec) == 80, "PrimRec layout");
+static_assert(sizeof(PrimRec) == 112, "PrimRec layout");
 // Device buffers of one raster pass, owned by the pipeline and grown on demand (szg_api.cpp).
 struct RasterBuffers
 {
