@@ -53,6 +53,9 @@ def main(argv=None):
                     help="end every frame with the blit onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) and write --out from it")
     ap.add_argument("--pipeline", default="deferred", metavar="deferred|compute-collection[:NAME]",
                     help="the rendering pipeline of Renderer::recordDraw (renderer.cpp:379-439)")
+    ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
+                    help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
+                         "(default), reference (the reference sampler's 1.0) or a number")
     args = ap.parse_args(argv)
 
     import torch
@@ -64,6 +67,10 @@ def main(argv=None):
         pipeline, shader = pl.parse_pipeline_option(args.pipeline)
     except ValueError as e:
         ap.error(f"--pipeline {e}")
+    try:
+        max_lod = pl.parse_mipmaps_option(args.mipmaps) if args.mipmaps is not None else None
+    except ValueError as e:
+        ap.error(f"--mipmaps {e}")
     # ---- scene: the editor's start-up scene, its cubes animated (editor.cpp:500-545) -----------------------------
     material = meshes.default_material()
     cv, ci = meshes.cube_mesh()
@@ -128,7 +135,7 @@ def main(argv=None):
             lib().szg_tick_mesh_instance(inst["animation"], inst["originals"], inst["transforms"], inst["n"], elapsed, dt, inst["models"],
                                          inst["mits"])
             scene_meshes.append(meshes.MeshInstanced(inst["vertices"], inst["indices"], [(0, len(inst["indices"]), material)],
-                                                     list(inst["models"])))
+                                                     list(inst["models"]), mipmaps=max_lod is not None))
             casters.append(abi.ShadowCaster(inst["bounds"], inst["transforms"], inst["n"], 1, 1, 0))
             for t in inst["transforms"]:
                 debug_lines.pushBox(t, inst["bounds"])  # renderer.cpp:355-365
@@ -144,6 +151,8 @@ def main(argv=None):
         if pipeline == "compute-collection":  # renderer.cpp:431-438: the collection only
             collection.recordDrawCommands(None, target, rect)
         else:
+            if max_lod is not None:  # the meshes of a frame are new uploads: their chains are registered with them
+                meshes.register_texture_mips(deferred, scene_meshes, max_lod)
             deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
             sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
             debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423

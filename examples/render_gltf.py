@@ -62,6 +62,9 @@ def main(argv=None):
                     help="blit the frame onto a WxH swapchain image (rgba8, bgra8 or a2b10g10r10) on the GPU and write --out from it")
     ap.add_argument("--pipeline", default="deferred", metavar="deferred|compute-collection[:NAME]",
                     help="the rendering pipeline of Renderer::recordDraw (renderer.cpp:379-439)")
+    ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
+                    help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
+                         "(default), reference (the reference sampler's 1.0) or a number")
     args = ap.parse_args(argv)
 
     import torch
@@ -72,6 +75,10 @@ def main(argv=None):
         pipeline, shader = pl.parse_pipeline_option(args.pipeline)
     except ValueError as e:
         ap.error(f"--pipeline {e}")
+    try:
+        max_lod = pl.parse_mipmaps_option(args.mipmaps) if args.mipmaps is not None else None
+    except ValueError as e:
+        ap.error(f"--mipmaps {e}")
 
     path = args.path
     if not path:
@@ -135,6 +142,10 @@ def main(argv=None):
         collection.writeExampleValues()
         collection.recordDrawCommands(None, target, rect)
     else:
+        if max_lod is not None:
+            for m in scene_meshes:
+                m.mipmaps = True  # chains are built with the upload, or now for a mesh that is already on the device
+            print(f"mip chains for {meshes.register_texture_mips(deferred, scene_meshes, max_lod)} textures, max_lod {max_lod:g}")
         deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
         sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     pl.recordOETF(None, target, W, H)

@@ -59,10 +59,16 @@ struct ImageView
     ImageView() = default;
     ImageView(ImageView const&) = delete;
     auto operator=(ImageView const&) -> ImageView& = delete;
-    ~ImageView() { (void)hipFree(data); }
+    ~ImageView()
+    {
+        (void)hipFree(data);
+        (void)hipFree(mipChain);
+    }
 
-    // detail::uploadImageToGPU + ImageView::allocate (assets.cpp:60-159, :257-313)
-    static auto upload(uint8_t const* rgba, uint32_t width, uint32_t height, bool srgb, std::string name) -> std::shared_ptr<ImageView const>
+    // detail::uploadImageToGPU + ImageView::allocate (assets.cpp:60-159, :257-313). `generateMips`: also build the full mip
+    // chain (szg/mipmaps.h) on the null stream; the view owns it. A chain that cannot be built leaves a one-level image.
+    static auto upload(uint8_t const* rgba, uint32_t width, uint32_t height, bool srgb, std::string name, bool generateMips = false)
+        -> std::shared_ptr<ImageView const>
     {
         auto view = std::make_shared<ImageView>();
         view->data = detail::uploadBytes(rgba, size_t{width} * height * 4);
@@ -75,14 +81,36 @@ struct ImageView
         view->height = height;
         view->srgb = srgb;
         view->name = std::move(name);
+        size_t const chainBytes = generateMips ? szg_mip_chain_bytes(width, height) : 0;
+        if (chainBytes > 0 && hipMalloc(&view->mipChain, chainBytes) == hipSuccess)
+        {
+            szg_texture const level0 = view->texture();
+            if (szg_record_generate_mipmaps(nullptr, &level0, view->mipChain, chainBytes) == SZG_OK)
+            {
+                view->mipLevels = szg_mip_level_count(width, height);
+            }
+            else
+            {
+                (void)hipFree(view->mipChain);
+                view->mipChain = nullptr;
+            }
+        }
+        if (chainBytes > 0 && view->mipLevels <= 1)
+        {
+            std::fprintf(stderr, "[szg] Failed to build the mip chain of image '%s'; it keeps one level.\n", view->name.c_str());
+        }
         return view;
     }
     [[nodiscard]] auto texture() const -> szg_texture { return szg_texture{data, width, height, width * 4, srgb ? 1u : 0u}; }
+    // the entry of this image for DeferredShadingPipeline::setTextureMips
+    [[nodiscard]] auto textureMips() const -> szg_texture_mips { return szg_texture_mips{data, mipChain, mipLevels}; }
 
     void* data{nullptr};
     uint32_t width{0}, height{0};
     bool srgb{false};
     std::string name{};
+    void* mipChain{nullptr}; // levels 1.. (szg/mipmaps.h "CHAIN LAYOUT"), or nullptr
+    uint32_t mipLevels{1};
 };
 
 struct MaterialData
@@ -132,9 +160,11 @@ class AssetLibrary
     };
 
     // assets.cpp:1286-1613: the three default maps and the two built-in meshes
-    static auto loadDefaultAssets() -> std::optional<AssetLibrary>
+    // `generateMips`: the library's switch (setGenerateMips), on from the default maps onwards
+    static auto loadDefaultAssets(bool generateMips = false) -> std::optional<AssetLibrary>
     {
         AssetLibrary library{};
+        library.m_generateMips = generateMips;
         std::vector<uint8_t> map(size_t{SZG_DEFAULT_MAP_DIMENSIONS} * SZG_DEFAULT_MAP_DIMENSIONS * 4);
         std::shared_ptr<ImageView const>* const targets[3] = {&library.m_defaultColorMap, &library.m_defaultNormalMap, &library.m_defaultORMMap};
         char const* const names[3] = {"texture_defaultColor", "texture_defaultNormal", "texture_defaultORM"};
@@ -145,7 +175,7 @@ class AssetLibrary
                 return std::nullopt;
             }
             *targets[kind] = ImageView::upload(map.data(), SZG_DEFAULT_MAP_DIMENSIONS, SZG_DEFAULT_MAP_DIMENSIONS, false,
-                                               library.deduplicateAssetName(names[kind]));
+                                               library.deduplicateAssetName(names[kind]), library.m_generateMips);
             if (*targets[kind] == nullptr)
             {
                 return std::nullopt;
@@ -195,7 +225,8 @@ class AssetLibrary
                 {
                     return;
                 }
-                if (auto view = ImageView::upload(t.rgba, t.width, t.height, t.srgb != 0, deduplicateAssetName(t.name)); view != nullptr)
+                if (auto view = ImageView::upload(t.rgba, t.width, t.height, t.srgb != 0, deduplicateAssetName(t.name), m_generateMips);
+                    view != nullptr)
                 {
                     m_textures.push_back(view);
                     slot = view;
@@ -232,7 +263,7 @@ class AssetLibrary
                                                      : "[szg] Failed to convert file to 32 bit RGBA image.\n");
             return nullptr;
         }
-        auto view = ImageView::upload(rgba, width, height, srgb, deduplicateAssetName("texture_" + filePath.stem().string()));
+        auto view = ImageView::upload(rgba, width, height, srgb, deduplicateAssetName("texture_" + filePath.stem().string()), m_generateMips);
         szg_free_rgba(rgba);
         if (view != nullptr)
         {
@@ -247,6 +278,24 @@ class AssetLibrary
     }
     [[nodiscard]] auto meshes() const -> std::span<std::shared_ptr<Mesh const> const> { return m_meshes; }
     [[nodiscard]] auto textures() const -> std::span<std::shared_ptr<ImageView const> const> { return m_textures; }
+    // szg/mipmaps.h: while the switch is on, every texture this library uploads (loadGLTFFromPath, loadTextureFromPath; the
+    // default maps when loadDefaultAssets(true) set it) gets a full mip chain, owned by its ImageView. Off by default.
+    void setGenerateMips(bool enable) { m_generateMips = enable; }
+    [[nodiscard]] auto generateMips() const -> bool { return m_generateMips; }
+    // The table entries of every texture of this library that carries a chain, for DeferredShadingPipeline::setTextureMips.
+    // Empty unless textures were loaded with the switch on.
+    [[nodiscard]] auto textureMips() const -> std::vector<szg_texture_mips>
+    {
+        std::vector<szg_texture_mips> entries;
+        for (auto const& view : m_textures)
+        {
+            if (view != nullptr && view->mipLevels > 1)
+            {
+                entries.push_back(view->textureMips());
+            }
+        }
+        return entries;
+    }
     [[nodiscard]] auto defaultMaterial() const -> MaterialData { return MaterialData{m_defaultORMMap, m_defaultNormalMap, m_defaultColorMap}; }
 
   private:
@@ -289,6 +338,7 @@ class AssetLibrary
     std::unordered_map<std::string, size_t> m_nameDuplicationCounters{};
     std::shared_ptr<ImageView const> m_defaultColorMap{}, m_defaultNormalMap{}, m_defaultORMMap{};
     std::vector<std::shared_ptr<ImageView const>> m_textures{};
+    bool m_generateMips{false};
     std::shared_ptr<Mesh const> m_meshPlane{}, m_meshCube{};
     std::vector<std::shared_ptr<Mesh const>> m_meshes{};
 };

@@ -35,6 +35,7 @@
 #include "szg/abi.h"
 #include "szg/compute_collection.h"
 #include "szg/debuglines.h"
+#include "szg/mipmaps.h"
 #include "szg/present.h"
 #include "szg/raster.h"
 #include "szg/host.h"
@@ -326,6 +327,13 @@ struct DeferredShadingPipeline
         return c;
     }
     void setConfiguration(Configuration c) { (void)szg_deferred_set_configuration(m_handle, &c); } // deferred.hpp:115
+    // szg/mipmaps.h: the mip chains of the material textures (copied; an empty span clears the table) and the sampler's
+    // maxLod: SZG_SAMPLER_MAX_LOD_REFERENCE is what the reference's sampler has (vulkanstructs.cpp:147-183).
+    auto setTextureMips(std::span<szg_texture_mips const> entries, float maxLod = SZG_SAMPLER_MAX_LOD_NONE) -> int
+    {
+        return detail::note(szg_deferred_set_texture_mips(m_handle, entries.data(), static_cast<uint32_t>(entries.size()), maxLod),
+                            "szg_deferred_set_texture_mips", m_lastStatus);
+    }
     [[nodiscard]] auto valid() const -> bool { return m_handle != nullptr; }
 
 private:

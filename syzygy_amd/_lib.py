@@ -1,6 +1,7 @@
 """Loader for the C-ABI shared library (syzygy_amd/csrc/libszg_hip.so)."""
 import ctypes
 import os
+import sys
 
 from . import abi
 
@@ -58,6 +59,14 @@ def lib():
             abi.bind(handle, abi.COMPUTE_COLLECTION_FUNCTIONS)
         except AttributeError as e:
             raise RuntimeError(f"{path} predates include/szg/compute_collection.h ({e}); rebuild the library") from e
+        try:
+            abi.bind(handle, abi.MIPMAP_FUNCTIONS)
+        except AttributeError as e:
+            if "SZG_HIP_LIBRARY" not in os.environ:
+                raise RuntimeError(f"{path} predates include/szg/mipmaps.h ({e}); rebuild the library") from e
+            # a library named explicitly for a comparison (tools/bench_raster_libraries.py --baseline: a parent commit's build)
+            # may predate the header: everything else works, and a mip entry point raises AttributeError when it is called
+            print(f"[szg] {path} predates include/szg/mipmaps.h ({e}): mip-mapped textures are unavailable with it", file=sys.stderr)
         _LIB = handle
     return _LIB
 

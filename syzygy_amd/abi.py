@@ -592,6 +592,22 @@ COMPUTE_COLLECTION_FUNCTIONS = {
     "szg_record_compute_collection": (C.c_int, [VP, U32, VP, U32, P(Image), U32, U32]),
 }
 
+# include/szg/mipmaps.h
+SZG_SAMPLER_MAX_LOD_REFERENCE = 1.0
+SZG_SAMPLER_MAX_LOD_NONE = 1000.0
+
+
+class TextureMips(C.Structure):
+    _fields_ = [("level0_data", VP), ("d_chain", VP), ("level_count", U32)]
+
+
+MIPMAP_FUNCTIONS = {
+    "szg_mip_level_count": (U32, [U32, U32]),
+    "szg_mip_chain_bytes": (C.c_size_t, [U32, U32]),
+    "szg_record_generate_mipmaps": (C.c_int, [VP, P(Texture), VP, C.c_size_t]),
+    "szg_deferred_set_texture_mips": (C.c_int, [VP, P(TextureMips), U32, C.c_float]),
+}
+
 
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""

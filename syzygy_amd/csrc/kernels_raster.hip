@@ -17,6 +17,7 @@
 #include "szg/exact_sign.h"
 #include "szg_device.hpp"
 #include "szg_launch.hpp"
+#include "szg_texture.hpp"
 
 namespace szg
 {
@@ -477,65 +478,9 @@ SZG_DEV Varyings interpolate(const PrimRec& t, const VertexOut v[3], float px, f
     return o;
 }
 
-// raster.h "textures": RGBA8, LINEAR, REPEAT, one level
-SZG_DEV float decode8(unsigned b, bool srgb)
-{
-    float const c = (float)b / 255.0f;
-    if (!srgb)
-    {
-        return c;
-    }
-    return c <= 0.04045f ? c / 12.92f : szg_powf((c + 0.055f) / 1.055f, 2.4f);
-}
-SZG_DEV int wrapIndex(float f, int n)
-{
-    float const fn = (float)n;
-    float const m = f - fn * floorf(f / fn);
-    int i = (int)m;
-    if (i >= n || i < 0)
-    {
-        i = 0;
-    }
-    return i;
-}
-// `unormTable[b]` = decode8(b, false), `srgbTable[b]` = decode8(b, true): the 36 texel decodes of a pixel are LDS
-// look-ups of values each computed once per workgroup by the same expression.
-SZG_DEV V3 sampleTexture(const szg_texture& tex, V2 st, const float* unormTable, const float* srgbTable)
-{
-    if (tex.data == nullptr || tex.width == 0u || tex.height == 0u)
-    {
-        return splat(0.0f);
-    }
-    int const W = (int)tex.width, H = (int)tex.height;
-    float const u = st.x * (float)W - 0.5f;
-    float const v = st.y * (float)H - 0.5f;
-    float const fu = floorf(u), fv = floorf(v);
-    float const a = u - fu, b = v - fv;
-    int const i0 = wrapIndex(fu, W), j0 = wrapIndex(fv, H);
-    int const i1 = (i0 + 1 == W) ? 0 : i0 + 1, j1 = (j0 + 1 == H) ? 0 : j0 + 1;
-    const unsigned char* base = static_cast<const unsigned char*>(tex.data);
-    unsigned const t00 = *reinterpret_cast<const unsigned*>(base + (size_t)j0 * tex.pitch_bytes + (size_t)i0 * 4u);
-    unsigned const t10 = *reinterpret_cast<const unsigned*>(base + (size_t)j0 * tex.pitch_bytes + (size_t)i1 * 4u);
-    unsigned const t01 = *reinterpret_cast<const unsigned*>(base + (size_t)j1 * tex.pitch_bytes + (size_t)i0 * 4u);
-    unsigned const t11 = *reinterpret_cast<const unsigned*>(base + (size_t)j1 * tex.pitch_bytes + (size_t)i1 * 4u);
-    const float* const table = tex.srgb != 0u ? srgbTable : unormTable;
-    float const w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
-    float r[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++)
-    {
-        unsigned const sh = (unsigned)ch * 8u;
-        r[ch] = w00 * table[(t00 >> sh) & 0xFFu] + w10 * table[(t10 >> sh) & 0xFFu] + w01 * table[(t01 >> sh) & 0xFFu] +
-                w11 * table[(t11 >> sh) & 0xFFu];
-    }
-    return mk3(r[0], r[1], r[2]);
-}
-
 // deferred/offscreen.frag:25-59
-SZG_DEV V3 perturbNormal(const szg_texture& normalMap, V3 N, V3 dPosDx, V3 dPosDy, V2 dUvDx, V2 dUvDy, V2 texcoord,
-                         const float* unormTable, const float* srgbTable)
+SZG_DEV V3 perturbNormal(V3 map, V3 N, V3 dPosDx, V3 dPosDy, V2 dUvDx, V2 dUvDy)
 {
-    V3 map = sampleTexture(normalMap, texcoord, unormTable, srgbTable);
     float const k = 128.0f / 127.0f;
     map = mk3(map.x * 255.0f / 127.0f - k, map.y * 255.0f / 127.0f - k, map.z * 255.0f / 127.0f - k); // :47
     map.y = -map.y;                                                                                    // :50
@@ -553,6 +498,9 @@ SZG_DEV V3 perturbNormal(const szg_texture& normalMap, V3 N, V3 dPosDx, V3 dPosD
 } // namespace
 
 // ---------------------------------------------------------------------------
+// MIPS = false: every map is sampled at level 0 (raster.h "textures"), the kernel of a pipeline without a mip table.
+// MIPS = true: each map goes through the trilinear sampler of mipmaps.h with the chain its draw carries.
+template <bool MIPS>
 __global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image gDiffuse, szg_image gSpecular, szg_image gNormal,
                                                      szg_image gPosition, szg_image gOrm, unsigned drawW, unsigned drawH,
                                                      unsigned localRows, RowMap rm, const RasterDraw* __restrict__ draws,
@@ -625,9 +573,13 @@ __global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image 
         Varyings const xl = isLeft ? in : ox, xr = isLeft ? ox : in;
         Varyings const yt = isTop ? in : oy, yb = isTop ? oy : in;
         V2 const dUvDx{xr.uv.x - xl.uv.x, xr.uv.y - xl.uv.y}, dUvDy{yb.uv.x - yt.uv.x, yb.uv.y - yt.uv.y};
-        V3 const N = perturbNormal(d.tex[1], in.normal, xr.world - xl.world, yb.world - yt.world, dUvDx, dUvDy, in.uv, s_unorm, s_srgb);
-        V3 const color = sampleTexture(d.tex[0], in.uv, s_unorm, s_srgb);
-        V3 const o = sampleTexture(d.tex[2], in.uv, s_unorm, s_srgb);
+        auto const sample = [&](int m) {
+            return MIPS ? sampleTextureMips(d.tex[m], TextureMips{d.mipChain[m], d.mipLevels[m], d.maxLod}, in.uv, dUvDx, dUvDy, s_unorm, s_srgb)
+                        : sampleTexture(d.tex[m], in.uv, s_unorm, s_srgb);
+        };
+        V3 const N = perturbNormal(sample(1), in.normal, xr.world - xl.world, yb.world - yt.world, dUvDx, dUvDy);
+        V3 const color = sample(0);
+        V3 const o = sample(2);
         dif = pack_half4(color.x, color.y, color.z, 1.0f);  // offscreen.frag:72, :75
         nrm = pack_half4(N.x, N.y, N.z, 0.0f);               // :68
         orm = pack_half4(o.x, o.y, o.z, 1.0f);               // :79
@@ -749,7 +701,7 @@ hipError_t launch_raster_setup(hipStream_t s, bool shadow, const RasterDraw* d_d
 
 hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                               const szg_gbuffer& g, const RasterDraw* d_draws, const RasterBuffers& b, unsigned primCount,
-                              const szg_camera_packed* d_cam, unsigned camIndex)
+                              const szg_camera_packed* d_cam, unsigned camIndex, bool mips)
 {
     unsigned const rows = tile.nranks <= 1u ? drawH : tile.local_rows;
     if (rows == 0u || drawW == 0u)
@@ -758,8 +710,16 @@ hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, uns
     }
     dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
     RowMap const rm{tile.block_rows, tile.rank, tile.nranks};
-    hipLaunchKernelGGL(k_raster_tile, grid, dim3(256), 0, s, scene.depth, g.diffuse, g.specular, g.normal, g.worldPosition,
-                       g.occlusionRoughnessMetallic, drawW, drawH, rows, rm, d_draws, b.prims, hierarchyOf(b, primCount), d_cam, camIndex);
+    if (mips)
+    {
+        hipLaunchKernelGGL(k_raster_tile<true>, grid, dim3(256), 0, s, scene.depth, g.diffuse, g.specular, g.normal, g.worldPosition,
+                           g.occlusionRoughnessMetallic, drawW, drawH, rows, rm, d_draws, b.prims, hierarchyOf(b, primCount), d_cam, camIndex);
+    }
+    else
+    {
+        hipLaunchKernelGGL(k_raster_tile<false>, grid, dim3(256), 0, s, scene.depth, g.diffuse, g.specular, g.normal, g.worldPosition,
+                           g.occlusionRoughnessMetallic, drawW, drawH, rows, rm, d_draws, b.prims, hierarchyOf(b, primCount), d_cam, camIndex);
+    }
     return hipGetLastError();
 }
 

@@ -8,14 +8,18 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/mipmaps.h"
 #ifdef SZG_LITERAL
 #define SZG_CONTRACT SZG_CONTRACT_NONE
 #endif
@@ -363,6 +367,9 @@ struct szg_deferred
     szg::RasterDraw* d_rasterDraws = nullptr;
     size_t rasterDrawCapacity = 0;
     szg::RasterBuffers raster;
+    // szg/mipmaps.h: the table of szg_deferred_set_texture_mips, looked up by level-0 pointer at record time
+    std::vector<szg_texture_mips> textureMips;
+    float textureMaxLod = SZG_SAMPLER_MAX_LOD_NONE;
 };
 
 void szg::set_last_error(const char* message)
@@ -1669,8 +1676,10 @@ namespace
 {
 // Flatten the rendered meshes into the reference's draw calls (deferred.cpp:624-699 / pipelines.cpp:738-800):
 // one draw per (mesh, surface), primitives numbered instance-major.
+// `mips` (G-buffer pass only): the pipeline's table of szg/mipmaps.h; `anyMips` = some draw carries more than one level.
 int collect_draws(const char* who, const szg_mesh_instanced* meshes, uint32_t meshCount, bool shadow,
-                  std::vector<szg::RasterDraw>& draws, uint32_t& primCount)
+                  std::vector<szg::RasterDraw>& draws, uint32_t& primCount, const szg_deferred* mips = nullptr,
+                  bool* anyMips = nullptr)
 {
     draws.clear();
     uint64_t prims = 0;
@@ -1719,6 +1728,37 @@ int collect_draws(const char* who, const szg_mesh_instanced* meshes, uint32_t me
                                           t.pitch_bytes < t.width * 4u || t.pitch_bytes % 4u != 0u))
                 {
                     return fail(SZG_ERR_INVALID_ARGUMENT, "%s: mesh %u surface %u has a malformed texture", who, i, k);
+                }
+            }
+            d.maxLod = 0.0f;
+            for (int t = 0; t < 3; t++)
+            {
+                d.mipChain[t] = nullptr;
+                d.mipLevels[t] = 1u;
+                if (mips == nullptr || d.tex[t].data == nullptr)
+                {
+                    continue;
+                }
+                // sorted by level0_data (szg_deferred_set_texture_mips)
+                auto const it = std::lower_bound(mips->textureMips.begin(), mips->textureMips.end(), d.tex[t].data,
+                                                 [](szg_texture_mips const& e, const void* key) { return std::less<const void*>()(e.level0_data, key); });
+                if (it == mips->textureMips.end() || it->level0_data != d.tex[t].data)
+                {
+                    continue;
+                }
+                uint32_t const full = szg_mip_level_count(d.tex[t].width, d.tex[t].height);
+                if (it->level_count > full)
+                {
+                    return fail(SZG_ERR_INVALID_ARGUMENT,
+                                "%s: mesh %u surface %u map %d is %ux%u (%u levels) but its mip table entry has level_count %u", who, i, k, t,
+                                d.tex[t].width, d.tex[t].height, full, it->level_count);
+                }
+                d.mipChain[t] = it->d_chain;
+                d.mipLevels[t] = it->level_count;
+                d.maxLod = mips->textureMaxLod;
+                if (it->level_count > 1u && anyMips != nullptr)
+                {
+                    *anyMips = true;
                 }
             }
             prims += (uint64_t)tris * m.instance_count;
@@ -1835,7 +1875,8 @@ int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect
     }
     std::vector<szg::RasterDraw> draws;
     uint32_t primCount = 0;
-    int rc = collect_draws("szg_deferred_record_gbuffer_raster", meshes, mesh_count, false, draws, primCount);
+    bool anyMips = false; // k_raster_tile<true> only when some draw of this call has a chain (szg/mipmaps.h)
+    int rc = collect_draws("szg_deferred_record_gbuffer_raster", meshes, mesh_count, false, draws, primCount, p, &anyMips);
     if (rc != SZG_OK)
     {
         return rc;
@@ -1854,7 +1895,123 @@ int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect
     SZG_HIP(szg::launch_raster_setup(s, false, p->d_rasterDraws, (unsigned)draws.size(), primCount, d_cameras, view_camera_index, nullptr,
                                      draw_rect.width, draw_rect.height, p->raster));
     SZG_HIP(szg::launch_raster_tile(s, *scene_texture, draw_rect.width, draw_rect.height, t, p->gbuffer, p->d_rasterDraws, p->raster,
-                                    primCount, d_cameras, view_camera_index));
+                                    primCount, d_cameras, view_camera_index, anyMips));
+    return SZG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Mip-mapped material textures (szg/mipmaps.h)
+// ---------------------------------------------------------------------------
+uint32_t szg_mip_level_count(uint32_t w, uint32_t h)
+{
+    if (w == 0u || h == 0u)
+    {
+        return 0u;
+    }
+    uint32_t levels = 1u;
+    for (uint32_t m = w > h ? w : h; m > 1u; m >>= 1)
+    {
+        levels++;
+    }
+    return levels;
+}
+
+size_t szg_mip_chain_bytes(uint32_t w, uint32_t h)
+{
+    size_t bytes = 0;
+    uint32_t const levels = szg_mip_level_count(w, h);
+    for (uint32_t k = 1u; k < levels; k++)
+    {
+        size_t const wk = (w >> k) > 0u ? (w >> k) : 1u, hk = (h >> k) > 0u ? (h >> k) : 1u;
+        bytes += wk * hk * 4u;
+    }
+    return bytes;
+}
+
+int szg_record_generate_mipmaps(void* stream, const szg_texture* level0, void* d_chain, size_t chain_bytes)
+{
+    if (level0 == nullptr || level0->data == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: NULL level0 or level0->data");
+    }
+    if (level0->width == 0u || level0->height == 0u || level0->width > 32768u || level0->height > 32768u)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: extent %ux%u outside 1..32768", level0->width, level0->height);
+    }
+    if (level0->pitch_bytes < level0->width * 4u || level0->pitch_bytes % 4u != 0u)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: pitch %u is smaller than a row of %u texels or no multiple of 4",
+                    level0->pitch_bytes, level0->width);
+    }
+    if (reinterpret_cast<uintptr_t>(level0->data) % 4u != 0u || reinterpret_cast<uintptr_t>(d_chain) % 4u != 0u)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: level0->data and d_chain must be aligned to 4 bytes");
+    }
+    size_t const need = szg_mip_chain_bytes(level0->width, level0->height);
+    if (chain_bytes < need)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: chain_bytes %zu, the chain of %ux%u needs %zu", chain_bytes,
+                    level0->width, level0->height, need);
+    }
+    if (need == 0u)
+    {
+        return SZG_OK;
+    }
+    if (d_chain == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: NULL d_chain");
+    }
+    SZG_HIP(szg::launch_generate_mipmaps(static_cast<hipStream_t>(stream), *level0, d_chain));
+    return SZG_OK;
+}
+
+int szg_deferred_set_texture_mips(szg_deferred_t* p, const szg_texture_mips* entries, uint32_t count, float max_lod)
+{
+    // the arguments first, the pipeline last: every refusal below names its cause without a device
+    if (count > 0u && entries == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: NULL entries with count %u", count);
+    }
+    if (!(max_lod >= 0.0f))
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: max_lod is negative or NaN");
+    }
+    for (uint32_t i = 0; i < count; i++)
+    {
+        if (entries[i].level0_data == nullptr)
+        {
+            return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: entry %u has a NULL level0_data", i);
+        }
+        if (entries[i].level_count == 0u)
+        {
+            return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: entry %u has level_count 0", i);
+        }
+        if (reinterpret_cast<uintptr_t>(entries[i].level0_data) % 4u != 0u || reinterpret_cast<uintptr_t>(entries[i].d_chain) % 4u != 0u)
+        {
+            return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: entry %u: level0_data and d_chain must be aligned to 4 bytes", i);
+        }
+        if (entries[i].level_count > 1u && entries[i].d_chain == nullptr)
+        {
+            return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: entry %u has %u levels and a NULL d_chain", i,
+                        entries[i].level_count);
+        }
+        for (uint32_t j = 0; j < i; j++)
+        {
+            if (entries[j].level0_data == entries[i].level0_data)
+            {
+                return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: entries %u and %u have the same level0_data (duplicate)",
+                            j, i);
+            }
+        }
+    }
+    if (p == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_texture_mips: NULL pipeline");
+    }
+    p->textureMips.assign(entries, entries + count);
+    std::sort(p->textureMips.begin(), p->textureMips.end(),
+              [](szg_texture_mips const& a, szg_texture_mips const& b) { return std::less<const void*>()(a.level0_data, b.level0_data); });
+    p->textureMaxLod = max_lod;
     return SZG_OK;
 }
 

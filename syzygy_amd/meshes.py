@@ -96,9 +96,10 @@ def inverse_transpose(m):
 
 class MeshInstanced:
     """One mesh with its surfaces and instance transforms. `surfaces` = [(first_index, index_count, material)], a
-    material being {"color"|"normal"|"orm": (uint8 [h, w, 4] array, srgb flag)}."""
+    material being {"color"|"normal"|"orm": (uint8 [h, w, 4] array, srgb flag)}. `mipmaps=True` builds a full mip chain for
+    every texture on upload (include/szg/mipmaps.h); register them with register_texture_mips()."""
 
-    def __init__(self, vertices, indices, surfaces, models, render=True, casts_shadow=True, name=""):
+    def __init__(self, vertices, indices, surfaces, models, render=True, casts_shadow=True, name="", mipmaps=False):
         self.name = name
         self.vertices = np.ascontiguousarray(vertices)
         self.indices = np.ascontiguousarray(indices, np.uint32)
@@ -106,6 +107,7 @@ class MeshInstanced:
         self.models = list(models)
         self.mits = [inverse_transpose(m) for m in self.models]  # scene.cpp:205-211
         self.render, self.casts_shadow = bool(render), bool(casts_shadow)
+        self.mipmaps = bool(mipmaps)
         self._models_np = np.array([np.array(m.m, np.float32) for m in self.models], np.float32).reshape(-1, 16)
         self._mits_np = np.array([np.array(m.m, np.float32) for m in self.mits], np.float32).reshape(-1, 16)
         self._device = None
@@ -116,6 +118,7 @@ class MeshInstanced:
         import torch
 
         if self._device is not None:
+            self._ensure_mips(self._device)
             return self._device
 
         def up(a):
@@ -127,8 +130,34 @@ class MeshInstanced:
             for key, (tex, _) in material.items():
                 if id(tex) not in d["textures"]:
                     d["textures"][id(tex)] = up(tex)
+        d["mips"] = {}
         self._device = d
+        self._ensure_mips(d)
         return d
+
+    def _ensure_mips(self, d):
+        """Chains for every texture while `mipmaps` is set, whenever it was set: built once, dropped when it is cleared."""
+        if not self.mipmaps:
+            d["mips"] = {}
+            return
+        from . import pipelines
+
+        for _, _, material in self.surfaces:
+            for key, (tex, srgb) in material.items():
+                if id(tex) not in d["mips"]:
+                    level0 = d["textures"][id(tex)].view(tex.shape[0], tex.shape[1], 4)
+                    d["mips"][id(tex)] = pipelines.generate_mipmaps(level0, srgb)
+
+
+    def device_texture(self, tex, device="cuda"):
+        """The device copy (uint8 tensor) of one of this mesh's texture arrays: its data_ptr() is what szg_texture.data holds."""
+        return self._to_device(device)["textures"][id(tex)]
+
+    def texture_mips(self, device="cuda"):
+        """[(level0 tensor, chain tensor, level_count)] of the chains built for this mesh's textures (mipmaps=True)."""
+        d = self._to_device(device)
+        shapes = {id(tex): tex.shape for _, _, material in self.surfaces for tex, _ in material.values()}
+        return [(d["textures"][k], chain, lib().szg_mip_level_count(shapes[k][1], shapes[k][0])) for k, chain in d["mips"].items()]
 
     def _struct(self, ptr_of, tex_ptr_of):
         n = len(self.surfaces)
@@ -165,6 +194,14 @@ def mesh_array(meshes, device=None):
     for i, m in enumerate(meshes):
         arr[i] = m.device_struct(device) if device is not None else m.host_struct()
     return arr
+
+
+def register_texture_mips(pipeline, meshes, max_lod=abi.SZG_SAMPLER_MAX_LOD_NONE, device="cuda"):
+    """Hand the chains of every mesh built with mipmaps=True to `pipeline` (DeferredShadingPipeline.setTextureMips); returns the
+    number of entries. No such mesh clears the table."""
+    entries = [e for m in meshes for e in m.texture_mips(device)]
+    pipeline.setTextureMips(entries, max_lod)
+    return len(entries)
 
 
 def reference_default_scene():

@@ -169,6 +169,50 @@ def recordOETF(cmd, sceneTexture, width, height, transferFunction=abi.SZG_OETF_S
 
 
 # ---------------------------------------------------------------------------
+# Mip-mapped material textures (include/szg/mipmaps.h)
+# ---------------------------------------------------------------------------
+def mip_level_shapes(width, height):
+    """[(w_k, h_k)] for k = 0 .. szg_mip_level_count - 1 (mipmaps.h "CHAIN LAYOUT")."""
+    return [(max(1, width >> k), max(1, height >> k)) for k in range(lib().szg_mip_level_count(int(width), int(height)))]
+
+
+def mip_chain_levels(chain, width, height):
+    """Views [h_k, w_k, 4] of levels 1.. of a packed chain (tensor or numpy array of bytes) of a width x height image."""
+    out, offset = [], 0
+    for w, h in mip_level_shapes(width, height)[1:]:
+        out.append(chain[offset:offset + w * h * 4].reshape(h, w, 4))
+        offset += w * h * 4
+    return out
+
+
+def parse_mipmaps_option(text):
+    """The examples' --mipmaps[=MAXLOD] switch -> the sampler's max_lod: 'none' (the switch alone) lifts the clamp, 'reference' is
+    the reference sampler's 1.0, else a number >= 0."""
+    if text in ("none", "reference"):
+        return abi.SZG_SAMPLER_MAX_LOD_NONE if text == "none" else abi.SZG_SAMPLER_MAX_LOD_REFERENCE
+    try:
+        value = float(text)
+    except ValueError:
+        value = -1.0
+    if not value >= 0.0:
+        raise ValueError(f"{text!r}: expected none, reference or a number >= 0")
+    return value
+
+
+def generate_mipmaps(texture, srgb, cmd=None):
+    """szg_record_generate_mipmaps: the packed chain (levels 1.., a uint8 CUDA tensor; empty for a 1x1 image) of an RGBA8 image,
+    a uint8 CUDA tensor [h, w, 4] whose rows may be strided (a pitch wider than w * 4)."""
+    if texture.dtype != torch.uint8 or texture.dim() != 3 or texture.shape[2] != 4 or texture.stride(2) != 1 or texture.stride(1) != 4:
+        raise ValueError("generate_mipmaps: expected a uint8 tensor [h, w, 4] with contiguous texels")
+    h, w = int(texture.shape[0]), int(texture.shape[1])
+    level0 = abi.Texture(texture.data_ptr(), w, h, int(texture.stride(0)) if h > 1 else w * 4, int(bool(srgb)))
+    nbytes = lib().szg_mip_chain_bytes(w, h)
+    chain = torch.empty(nbytes, dtype=torch.uint8, device=texture.device)
+    check(lib().szg_record_generate_mipmaps(_stream_handle(cmd), C.byref(level0), C.c_void_p(chain.data_ptr() if nbytes else None), nbytes))
+    return chain
+
+
+# ---------------------------------------------------------------------------
 # Present pass (include/szg/present.h)
 # ---------------------------------------------------------------------------
 def _as_rect(r):
@@ -488,6 +532,19 @@ class DeferredShadingPipeline:
             int(atmosphericDirectionalLightsCount), C.c_void_p(directionalLights.deviceAddress()),
             int(directionalLights.deviceSize()), spots, n_spot, int(viewCameraIndex), C.c_void_p(cameras.deviceAddress()),
             arr, len(meshes)))
+
+    def setTextureMips(self, entries, max_lod=abi.SZG_SAMPLER_MAX_LOD_NONE):
+        """szg_deferred_set_texture_mips: `entries` = [(level0, chain, level_count)], level0 and chain CUDA tensors (kept alive
+        by the pipeline until the table is replaced) or device addresses; an empty list clears the table. `max_lod` is the
+        sampler's maxLod: abi.SZG_SAMPLER_MAX_LOD_REFERENCE (1.0, what the reference's sampler has) or _NONE."""
+        entries = list(entries)
+        table = (abi.TextureMips * max(len(entries), 1))()
+        for i, (level0, chain, levels) in enumerate(entries):
+            table[i].level0_data = level0.data_ptr() if hasattr(level0, "data_ptr") else level0
+            table[i].d_chain = (chain.data_ptr() or None) if hasattr(chain, "data_ptr") else chain
+            table[i].level_count = int(levels)
+        check(lib().szg_deferred_set_texture_mips(self._h, table if entries else None, len(entries), float(max_lod)))
+        self._mip_keep = entries
 
     def gbuffer(self):
         return lib().szg_deferred_gbuffer(self._h).contents
