@@ -25,8 +25,7 @@
 #include <new>
 #include <thread>
 
-#include "szg/abi.h"
-#include "szg_internal.hpp"
+#include "api_common.hpp"
 
 namespace
 {
@@ -168,28 +167,7 @@ const Rccl& rccl()
     return g_rccl;
 }
 
-// DeviceGuard of szg_api.cpp: a communicator lives on the device it was created on
-struct DeviceGuard
-{
-    int previous = -1;
-    bool switched = false;
-    explicit DeviceGuard(int device)
-    {
-        if (hipGetDevice(&previous) == hipSuccess && previous != device)
-        {
-            switched = hipSetDevice(device) == hipSuccess;
-        }
-    }
-    ~DeviceGuard()
-    {
-        if (switched)
-        {
-            (void)hipSetDevice(previous);
-        }
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
+using szg::DeviceGuard; // a communicator lives on the device it was created on
 
 int fail(int code, const char* fmt, const char* a = "", const char* b = "")
 {

@@ -8,6 +8,6 @@
 
 namespace szg
 {
-// sets the calling thread's szg_last_error() text (defined in szg_api.cpp)
+// sets the calling thread's szg_last_error() text (defined in api_core.cpp)
 void set_last_error(const char* message);
 } // namespace szg

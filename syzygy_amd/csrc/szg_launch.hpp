@@ -1,4 +1,4 @@
-// szg_launch.hpp — internal launch interface between the C-ABI layer (szg_api.cpp)
+// szg_launch.hpp — internal launch interface between the C-ABI layer (api_*.cpp)
 // and the kernel translation units. Not part of the public boundary.
 #pragma once
 
@@ -164,7 +164,7 @@ struct PrimRec
     float facing; // +1 front, -1 back: the factor a, b, c carry
 };
 static_assert(sizeof(PrimRec) == 112, "PrimRec layout");
-// Device buffers of one raster pass, owned by the pipeline and grown on demand (szg_api.cpp).
+// Device buffers of one raster pass, owned by the pipeline and grown on demand (api_raster.cpp).
 struct RasterBuffers
 {
     PrimRec* prims = nullptr;       // [capacity] submission order
@@ -215,7 +215,7 @@ struct DebugLineRec
     unsigned major;       // 0: x-major, 1: y-major
 };
 static_assert(sizeof(DebugLineRec) == 48, "DebugLineRec layout");
-// Device scratch of one pipeline object, sized at creation from its vertex capacity (szg_api.cpp).
+// Device scratch of one pipeline object, sized at creation from its vertex capacity (api_debuglines.cpp).
 struct DebugLineBuffers
 {
     DebugLineRec* recs = nullptr;          // [lines]

@@ -15,7 +15,7 @@
 
 namespace szg
 {
-void set_last_error(const char*) {} // the library's own definition lives in szg_api.cpp (HIP); not needed here
+void set_last_error(const char*) {} // the library's own definition lives in api_core.cpp (HIP); not needed here
 } // namespace szg
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;

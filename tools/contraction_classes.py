@@ -10,6 +10,7 @@ syzygy_amd/csrc/variants/ (git-ignored .so files; they travel to the GPU box wit
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -38,29 +39,12 @@ def default_masks():
 
 
 def build(masks):
-    os.makedirs(VAR, exist_ok=True)
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS \?= (.*)$", mk, re.M).group(1).replace("$(ARCH)", "gfx950")
-    sched = dict(re.findall(r"^SCHED_(\w+) = (.*)$", mk, re.M))
-    shared = ["kernels_raster_sort.o", "host_scene.o", "host_assets.o", "szg_comm.o"]  # no contraction site in these
+    # the unit list, the flags and the link are the Makefile's own (its `variant` rule): a variant is the whole library
     for m in masks:
-        so = os.path.join(VAR, f"libszg_hip_c{m:04x}.so")
-        objs = []
-        procs = []
-        for tu in ("kernels_lut", "kernels_deferred", "kernels_composite", "kernels_raster", "szg_api"):
-            src = tu + (".cpp" if tu == "szg_api" else ".hip")
-            obj = os.path.join(VAR, f"{tu}_c{m:04x}.o")
-            cmd = f"/opt/rocm/bin/hipcc {flags} {sched.get(tu, '')} -DSZG_CONTRACT=0x{m:04x}u -I../../include -I. -x hip -c {src} -o {obj}"
-            procs.append(subprocess.Popen(cmd, shell=True, cwd=CSRC))
-            objs.append(obj)
-        for p in procs:
-            if p.wait() != 0:
-                raise SystemExit(f"build of mask {m:#x} failed")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so] + objs +
-                       [os.path.join(CSRC, o) for o in shared] + ["-ldl"], check=True)
-        for o in objs:
-            os.remove(o)
-        print("built", so, flush=True)
+        name = f"libszg_hip_c{m:04x}.so"
+        subprocess.run(["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 1)), f"MASK={m:04x}", f"variants/{name}"], check=True)
+        shutil.rmtree(os.path.join(VAR, f"c{m:04x}"))  # the variant's objects
+        print("built", os.path.join(VAR, name), flush=True)
 
 
 def run(outdir, masks):
