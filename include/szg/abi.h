@@ -184,6 +184,16 @@ typedef enum szg_format
     SZG_FORMAT_A2B10G10R10_UNORM = 7   /* 4 B/texel : one little-endian dword, R bits 0-9, G 10-19, B 20-29, A 30-31 */
 } szg_format;
 
+/* An image may be allocated larger than what a pass draws, as the reference's are (scene texture and G-buffer at a capacity
+ * of 4096^2, renderer.hpp:93-96, drawn into at the top-left drawExtent): `width` / `height` are the ALLOCATED extent, every
+ * image of a call has its own `pitch_bytes`, and a record_* entry point accepts any image at least as large as its draw rect
+ * (the rows of its tile). The tested rule (tests/test_gpu_capacity_extent.py): the deferred, sky-view, raster and debug-line
+ * passes neither read nor write a texel outside the draw rect, nor a byte of row padding - the values inside it do not depend
+ * on the allocated extent or the pitch - and a call that refuses one of its images (too small, a pitch below width * texel
+ * size or no multiple of it, a misaligned pointer) has written to none of them, the chained record_draw_commands calls
+ * included. Exceptions, documented where they are declared: szg_record_oetf, whose extent is the caller's own argument, and
+ * szg_record_compute_collection (szg/compute_collection.h), which like the reference spills up to 15 columns and rows past
+ * its extent where the image has them. */
 typedef struct szg_image
 {
     void* data;           /* device pointer; NULL = absent */
@@ -470,7 +480,9 @@ int szg_deferred_record_draw_commands(
     const szg_spot_light_packed* h_spot_lights, uint32_t spot_light_count, uint32_t view_camera_index,
     const szg_camera_packed* d_cameras, const szg_fill_scene* geometry);
 
-/* The two device passes of recordDrawCommands, individually. */
+/* The two device passes of recordDrawCommands, individually. Each checks the whole scene texture (colour, depth for the
+ * G-buffer pass, debug_color when present), not only the planes it writes: what the next pass of the frame would refuse
+ * is refused by the first, and szg_deferred_record_draw_commands refuses before it has recorded anything. */
 int szg_deferred_record_gbuffer_fill(szg_deferred_t* p, void* stream, szg_rect draw_rect, const szg_rowtile* tile,
                                      const szg_scene_texture* scene_texture, uint32_t view_camera_index,
                                      const szg_camera_packed* d_cameras, const szg_fill_scene* geometry);

@@ -114,7 +114,9 @@ typedef struct szg_mesh_instanced
 
 /* The G-buffer pass of DeferredShadingPipeline::recordDrawCommands (deferred.cpp:493-713): clears the five
  * G-buffer planes and scene_texture->depth over the draw rect and rasterises every rendered mesh into them.
- * Row tiles as in abi.h (a rank rasterises only its rows). */
+ * Row tiles as in abi.h (a rank rasterises only its rows). The whole scene texture is checked, as by
+ * szg_deferred_record_gbuffer_fill: a missing or malformed colour image (or debug_color, when present) is refused although
+ * this pass writes neither - a depth-only caller hands in the colour image the lights pass of the frame will need. */
 int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect draw_rect, const szg_rowtile* tile,
                                        const szg_scene_texture* scene_texture, uint32_t view_camera_index,
                                        const szg_camera_packed* d_cameras, const szg_mesh_instanced* meshes,

@@ -230,3 +230,21 @@ struct szg_deferred
     std::vector<szg_texture_mips> textureMips;
     float textureMaxLod = SZG_SAMPLER_MAX_LOD_NONE;
 };
+
+namespace szg
+{
+// Every refusal of an image or light argument of szg_deferred_record_lights without recording anything (api_deferred.cpp),
+// reported under `caller`; `needDepth` when the same call also records a G-buffer pass into the scene texture. `plan`
+// (optional) receives what the checks resolved.
+struct LightsPlan
+{
+    TileArgs tile{};
+    unsigned nDir = 0; // directional lights behind the skipped atmospheric ones
+    bool empty = false; // zero-extent draw rect: nothing to record
+};
+int validate_lights(const char* caller, szg_deferred_t* p, szg_rect draw_rect, const szg_rowtile* tile,
+                    const szg_scene_texture* scene_texture, uint32_t atmospheric_directional_lights_count,
+                    const szg_directional_light_packed* d_directional_lights, uint32_t directional_light_count,
+                    const szg_spot_light_packed* h_spot_lights, uint32_t spot_light_count, const szg_camera_packed* d_cameras,
+                    bool needDepth, LightsPlan* plan);
+} // namespace szg

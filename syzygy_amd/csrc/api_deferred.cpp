@@ -177,8 +177,8 @@ int szg_deferred_record_gbuffer_fill(szg_deferred_t* p, void* stream, szg_rect d
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
-    if (!check_gbuffer(&p->gbuffer, draw_rect.width, t.local_rows) ||
-        !check_image(scene_texture->depth, SZG_FORMAT_D32_SFLOAT, draw_rect.width, t.local_rows, "scene_texture.depth"))
+    // the whole scene texture, not only the depth this pass writes: the lights pass of the same frame would refuse it
+    if (!check_gbuffer(&p->gbuffer, draw_rect.width, t.local_rows) || !check_scene(scene_texture, draw_rect.width, t.local_rows, true))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
@@ -198,55 +198,85 @@ int szg_deferred_record_gbuffer_fill(szg_deferred_t* p, void* stream, szg_rect d
     return SZG_OK;
 }
 
+} // extern "C"
+
+// Every refusal of an image or light argument of szg_deferred_record_lights, with nothing recorded, reported under the
+// name of the entry point that was called: szg_deferred_record_draw_commands[_meshes] ask first, so that a frame whose lights
+// pass would be refused has not already had its G-buffer and depth rewritten. (What the geometry passes refuse about
+// their geometry itself - a bad checker cell, a malformed mesh table - is still found after the shadow passes, which write
+// only maps the pipeline owns.)
+int szg::validate_lights(const char* caller, szg_deferred_t* p, szg_rect draw_rect, const szg_rowtile* tile,
+                         const szg_scene_texture* scene_texture, uint32_t atmospheric_directional_lights_count,
+                         const szg_directional_light_packed* d_directional_lights, uint32_t directional_light_count,
+                         const szg_spot_light_packed* h_spot_lights, uint32_t spot_light_count, const szg_camera_packed* d_cameras,
+                         bool needDepth, LightsPlan* plan)
+{
+    if (p == nullptr || d_cameras == nullptr || scene_texture == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: NULL argument", caller);
+    }
+    if (!check_rect(draw_rect, caller))
+    {
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
+    if (directional_light_count > 0u && d_directional_lights == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: directional lights NULL", caller);
+    }
+    if (spot_light_count > 0u && h_spot_lights == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: spot lights NULL", caller);
+    }
+    if (spot_light_count > p->desc.max_spot_lights)
+    {
+        return fail(SZG_ERR_CAPACITY, "%s: %u spot lights exceed the capacity %u", caller, spot_light_count, p->desc.max_spot_lights);
+    }
+    unsigned const skip = atmospheric_directional_lights_count;
+    LightsPlan out{};
+    out.nDir = directional_light_count > skip ? directional_light_count - skip : 0u;
+    if (out.nDir > p->maxDirectional)
+    {
+        return fail(SZG_ERR_CAPACITY, "%s: %u directional lights exceed the capacity %u", caller, out.nDir, p->maxDirectional);
+    }
+    out.empty = draw_rect.width == 0u || draw_rect.height == 0u;
+    if (!out.empty)
+    {
+        if (!resolve_tile(tile, draw_rect.height, out.tile))
+        {
+            return SZG_ERR_INVALID_ARGUMENT;
+        }
+        if (!check_scene(scene_texture, draw_rect.width, out.tile.local_rows, needDepth) ||
+            !check_gbuffer(&p->gbuffer, draw_rect.width, out.tile.local_rows))
+        {
+            return SZG_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (plan != nullptr)
+    {
+        *plan = out;
+    }
+    return SZG_OK;
+}
+
+extern "C" {
+
 int szg_deferred_record_lights(szg_deferred_t* p, void* stream, szg_rect draw_rect, const szg_rowtile* tile,
                                const szg_scene_texture* scene_texture, uint32_t atmospheric_directional_lights_count,
                                const szg_directional_light_packed* d_directional_lights, uint32_t directional_light_count,
                                const szg_spot_light_packed* h_spot_lights, uint32_t spot_light_count, uint32_t view_camera_index,
                                const szg_camera_packed* d_cameras)
 {
-    if (p == nullptr || d_cameras == nullptr || scene_texture == nullptr)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_record_lights: NULL argument");
-    }
-    if (!check_rect(draw_rect, "szg_deferred_record_lights"))
-    {
-        return SZG_ERR_INVALID_ARGUMENT;
-    }
-    DeviceGuard const guard(p->device);
-    if (directional_light_count > 0u && d_directional_lights == nullptr)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_record_lights: directional lights NULL");
-    }
-    if (spot_light_count > 0u && h_spot_lights == nullptr)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_record_lights: spot lights NULL");
-    }
-    if (spot_light_count > p->desc.max_spot_lights)
-    {
-        return fail(SZG_ERR_CAPACITY, "szg_deferred_record_lights: %u spot lights exceed the capacity %u", spot_light_count,
-                    p->desc.max_spot_lights);
-    }
-    unsigned const skip = atmospheric_directional_lights_count;
-    unsigned const nDir = directional_light_count > skip ? directional_light_count - skip : 0u;
-    if (nDir > p->maxDirectional)
-    {
-        return fail(SZG_ERR_CAPACITY, "szg_deferred_record_lights: %u directional lights exceed the capacity %u", nDir,
-                    p->maxDirectional);
-    }
-    if (draw_rect.width == 0u || draw_rect.height == 0u)
+    LightsPlan plan{};
+    SZG_TRY_RC(validate_lights("szg_deferred_record_lights", p, draw_rect, tile, scene_texture, atmospheric_directional_lights_count,
+                               d_directional_lights, directional_light_count, h_spot_lights, spot_light_count, d_cameras, false, &plan));
+    if (plan.empty)
     {
         return SZG_OK;
     }
-    szg::TileArgs t{};
-    if (!resolve_tile(tile, draw_rect.height, t))
-    {
-        return SZG_ERR_INVALID_ARGUMENT;
-    }
-    if (!check_scene(scene_texture, draw_rect.width, t.local_rows, false) ||
-        !check_gbuffer(&p->gbuffer, draw_rect.width, t.local_rows))
-    {
-        return SZG_ERR_INVALID_ARGUMENT;
-    }
+    DeviceGuard const guard(p->device);
+    unsigned const skip = atmospheric_directional_lights_count;
+    unsigned const nDir = plan.nDir;
+    szg::TileArgs const t = plan.tile;
     hipStream_t const s = static_cast<hipStream_t>(stream);
 
     // deferred.cpp:458-474: upload the spot lights to the pipeline's own buffer
@@ -317,6 +347,9 @@ int szg_deferred_record_draw_commands(szg_deferred_t* p, void* stream, szg_rect 
                                       uint32_t spot_light_count, uint32_t view_camera_index, const szg_camera_packed* d_cameras,
                                       const szg_fill_scene* geometry)
 {
+    SZG_TRY_RC(validate_lights("szg_deferred_record_draw_commands", p, draw_rect, tile, scene_texture, atmospheric_directional_lights_count,
+                               d_directional_lights, directional_light_count, h_spot_lights, spot_light_count, d_cameras,
+                               geometry != nullptr, nullptr));
     if (geometry != nullptr)
     {
         // deferred.cpp:480-490 shadow maps, then :493-713 the G-buffer pass

@@ -200,8 +200,8 @@ int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
-    if (!check_gbuffer(&p->gbuffer, draw_rect.width, t.local_rows) ||
-        !check_image(scene_texture->depth, SZG_FORMAT_D32_SFLOAT, draw_rect.width, t.local_rows, "scene_texture.depth"))
+    // the whole scene texture, not only the depth this pass writes: the lights pass of the same frame would refuse it
+    if (!check_gbuffer(&p->gbuffer, draw_rect.width, t.local_rows) || !check_scene(scene_texture, draw_rect.width, t.local_rows, true))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
@@ -392,6 +392,9 @@ int szg_deferred_record_draw_commands_meshes(szg_deferred_t* p, void* stream, sz
                                              const szg_mesh_instanced* meshes, uint32_t mesh_count)
 {
     // deferred.cpp:480-490 shadow maps, :493-713 G-buffer pass, :715-787 lights
+    SZG_TRY_RC(validate_lights("szg_deferred_record_draw_commands_meshes", p, draw_rect, tile, scene_texture,
+                               atmospheric_directional_lights_count, d_directional_lights, directional_light_count, h_spot_lights,
+                               spot_light_count, d_cameras, true, nullptr));
     SZG_TRY_RC(szg_deferred_record_shadow_raster(p, stream, d_directional_lights, directional_light_count, h_spot_lights, spot_light_count,
                                                meshes, mesh_count));
     SZG_TRY_RC(szg_deferred_record_gbuffer_raster(p, stream, draw_rect, tile, scene_texture, view_camera_index, d_cameras, meshes, mesh_count));

@@ -553,11 +553,14 @@ class DeferredShadingPipeline:
         return lib().szg_deferred_shadow_maps(self._h).contents
 
     def setShadowMap(self, index, tensor):
-        """Attach a caller-owned D32F map (2-D float32 CUDA tensor) to slot `index`, or detach with None."""
+        """Attach a caller-owned D32F map (2-D float32 CUDA tensor whose rows may be padded: the pitch is the row stride) to
+        slot `index`, or detach with None."""
         if tensor is None:
             check(lib().szg_deferred_set_shadow_map(self._h, int(index), None))
             return
-        im = _image(tensor, tensor.shape[1], tensor.shape[0], abi.SZG_FORMAT_D32_SFLOAT)
+        if tensor.dtype != torch.float32:
+            raise ValueError(f"a shadow map holds float32 depths, got {tensor.dtype}")
+        im = _strided_image(tensor, abi.SZG_FORMAT_D32_SFLOAT, 1)
         check(lib().szg_deferred_set_shadow_map(self._h, int(index), C.byref(im)))
 
     def getConfiguration(self):

@@ -124,11 +124,13 @@ struct DefaultScene
 // The engine's own frame, written the way Editor::run + Renderer::recordDraw write it (editor.cpp:500-545, renderer.cpp:278-443):
 // asset library -> Scene::defaultScene -> ticks -> shadow bounds -> Renderer::recordDraw. Everything here is the
 // header-only mirrors of include/szg/{assets,scene,pipelines}.hpp.
-int engineFrame(const char* outPath, uint32_t W, uint32_t H, int ticks)
+// With capW x capH the renderer and the scene texture are allocated at that capacity and the frame is drawn into the top-left
+// W x H of them, as the engine does (renderer.hpp:93-96: 4096^2 whatever the viewport).
+int engineFrame(const char* outPath, uint32_t W, uint32_t H, int ticks, uint32_t capW, uint32_t capH)
 {
     auto library = szg::AssetLibrary::loadDefaultAssets();
-    auto renderer = szg::Renderer::create(W, H, 512);
-    auto sceneTexture = szg::SceneTexture::create(W, H);
+    auto renderer = szg::Renderer::create(capW, capH, 512);
+    auto sceneTexture = szg::SceneTexture::create(capW, capH);
     if (!library.has_value() || !renderer.has_value() || !sceneTexture)
     {
         std::fprintf(stderr, "setup failed: %s\n", szg_last_error());
@@ -171,13 +173,19 @@ int main(int argc, char** argv)
 {
     if (argc < 4)
     {
-        std::fprintf(stderr, "usage: record_draw out.bin width height [meshes | tiled [rank nranks idfile] | gltf <file> [loader flags] | scene [ticks]]\n");
+        std::fprintf(stderr, "usage: record_draw out.bin width height [meshes | tiled [rank nranks idfile] | gltf <file> [loader flags] | scene [ticks [capacityWidth capacityHeight]]]\n");
         return 2;
     }
     uint32_t const W = (uint32_t)std::atoi(argv[2]), H = (uint32_t)std::atoi(argv[3]);
     if (argc > 4 && std::strcmp(argv[4], "scene") == 0)
     {
-        return engineFrame(argv[1], W, H, argc > 5 ? std::atoi(argv[5]) : 3);
+        uint32_t const capW = argc > 7 ? (uint32_t)std::atoi(argv[6]) : W, capH = argc > 7 ? (uint32_t)std::atoi(argv[7]) : H;
+        if (capW < W || capH < H)
+        {
+            std::fprintf(stderr, "capacity %ux%u smaller than the frame %ux%u\n", capW, capH, W, H);
+            return 2;
+        }
+        return engineFrame(argv[1], W, H, argc > 5 ? std::atoi(argv[5]) : 3, capW, capH);
     }
     bool const gltf = argc > 5 && std::strcmp(argv[4], "gltf") == 0;
     bool const realMeshes = gltf || (argc > 4 && std::strcmp(argv[4], "meshes") == 0);

@@ -254,6 +254,25 @@ def test_cpp_engine_frame_scene_and_renderer_match_oracle(tmp_path):
     assert np.abs(got.astype(np.int32) - frame.color.astype(np.int32)).max() <= 1
 
 
+def test_cpp_engine_frame_inside_a_capacity_allocation_equals_the_tight_one(tmp_path):
+    """The engine's configuration (renderer.hpp:93-96, scenetexture.hpp:21-25): Renderer::create and SceneTexture::create at a
+    capacity extent, sceneSubregion {0, 0, W, H} inside it. The 70x37 frame drawn into 96x48 images - shadow raster, G-buffer
+    raster, lights, sky-view pipeline, read back with the image's pitch - is the file of the tight run byte for byte."""
+    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw"], check=True)
+    exe = os.path.join(HERE, "cpp", "record_draw")
+    W, H, TICKS = 70, 37, 2
+    files = {}
+    for name, extra in (("tight", []), ("capacity", ["96", "48"])):
+        out = tmp_path / f"frame_{name}.bin"
+        r = subprocess.run([exe, str(out), str(W), str(H), "scene", str(TICKS)] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        files[name] = out.read_bytes()
+    assert len(files["tight"]) == W * H * 8
+    assert files["capacity"] == files["tight"]
+    frame = np.frombuffer(files["tight"], np.uint16).reshape(H, W, 4)
+    assert (frame[..., 3] == 65535).all() and len(np.unique(frame[..., :3].reshape(-1, 3), axis=0)) > 100
+
+
 def test_cpp_tiled_frame_through_the_c_abi_collectives(tmp_path):
     """tests/cpp/record_draw.cpp `tiled`: a C++ caller (no Python, no torch) renders the row-tiled frame as the one rank of a
     world of one - szg_rowtile_comm over RCCL, the sky-view LUT row slice + in-place all-gather, the tile gather to the root,
