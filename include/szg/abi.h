@@ -379,7 +379,40 @@ int szg_skyview_record_composite(szg_skyview_t* p, void* stream, const szg_scene
  *   transmittance = sampleTransmittanceLUT_Segment(position, position + d_k * direction)  (common.glinl:114-136)
  * with direction(i, j) the camera.comp:324-328 view ray through the froxel centre ((i + .5) / W, (j + .5) / H) and
  * d_k = (k + .5) / D * max_distance_mm; they are parity-checked against the oracle. Only their trilinear USE by
- * szg_skyview_record_composite_fast() is approximate, so that mode is never part of the parity frame. */
+ * szg_skyview_record_composite_fast() is approximate, so that mode is never part of the parity frame.
+ *
+ * THE FETCH of the fast composite. APPROXIMATE with respect to the reference, EXACT with respect to this rule (the oracle's
+ * oracle_aerial_sample / oracle_composite_fast evaluate it; tests/test_gpu_fast_composite.py holds the kernel to them bit for
+ * bit). For the geometry pixel in column x and GLOBAL row gy (the row of the whole frame, also in a row-tiled launch) of a
+ * drawW x drawH draw rectangle, with `dist` = length(surfacePosition - cameraPosition) in Mm as computeGeometryLuminanceTransfer
+ * computes it (camera.comp:272), W x H x D the volume's size and maxDistance the max_distance_mm of the volume recorded last,
+ * every operation in binary32, rounded once each, in this order:
+ *   sx   = float(x) / float(drawW),  sy = float(gy) / float(drawH)        (no pixel-centre offset, as camera.comp:324-328)
+ *   fz   = dist / maxDistance * D - 0.5                                   (quotient, product, difference: three roundings)
+ *   ramp = fz < 0 ? max(dist / (0.5 * maxDistance / D), 0) : 1            (0.5 * maxDistance first, then / D, then dist / that)
+ *   z    = min(max(fz, 0), D - 1)                                         (max / min return the other operand for a NaN one)
+ *   k0   = int(floor(z)),  k1 = min(k0 + 1, D - 1),  wz = z - float(k0)
+ *   l0, l1 = the bilinear taps of slices k0 and k1 at (sx, sy) with the LUT sampler's rule (the one every LINEAR /
+ *          CLAMP_TO_EDGE LUT fetch of this library uses): u = sx * W - 0.5, v = sy * H - 0.5, i0 = floor(u), j0 = floor(v),
+ *          a = u - i0, b = v - j0, i1 = i0 + 1, j1 = j0 + 1, all four indices clamped to the edge AFTER the weights are
+ *          taken, tap = w11 * t11 + (w01 * t01 + (w10 * t10 + w00 * t00)) with w00 = (1 - a)(1 - b), w10 = a (1 - b),
+ *          w01 = (1 - a) b, w11 = a b; froxel (i, j, k) is texel (i, k * H + j) of the luminance image
+ *   aerial = (l0 * (1 - wz) + l1 * wz) * ramp                              (per channel; two products, a sum, a product)
+ *   transfer = surfaceTransfer + aerial                                   (where the reference adds its march, camera.comp:277)
+ * Contraction (szg/contraction.h): the only sites are those inside the bilinear tap, SZG_C_TEXCOORD for u and v and
+ * SZG_C_BILINEAR for the three sums of the tap; every other product above is rounded by itself, whatever SZG_CONTRACT says.
+ * What follows from the rule, and is part of it:
+ *   dist = 0     fz = -0.5, ramp = 0, k0 = 0, wz = 0: aerial = (l0 * 1 + l1 * 0) * 0 = +0 for finite non-negative froxels
+ *   dist < d_0   slice 0's tap, scaled linearly by dist / d_0 (denormal distances included: no flush to zero)
+ *   fz >= D - 1  (dist at or behind the last slice centre d_(D-1), as far as the roundings of fz tell; dist = +inf)
+ *                z = D - 1, k0 = k1 = D - 1, wz = 0: slice D - 1's tap (l0 * 1 + l1 * 0)
+ *   dist = NaN   fz = NaN, the comparison is false so ramp = 1, max(NaN, 0) = 0 so z = 0: slice 0's tap. (Such a pixel is NaN
+ *                all the same: its transmittance to the surface is.)
+ *   A non-finite froxel under a ZERO weight is not skipped: 0 * NaN = 0 * inf = NaN, in the bilinear weights (a = 0 or b = 0:
+ *   a pixel on a froxel centre is poisoned by its neighbours; at the edge the clamped index names the same froxel twice), in
+ *   the slice weights (wz = 0: slice k1 poisons an exact slice centre; behind the last slice k1 = k0) and in the ramp
+ *   (dist = 0 under a non-finite tap gives NaN, not 0). Non-finite froxels occur in ordinary use (froxel rays that run into
+ *   the ground). */
 #define SZG_AERIAL_W 32u
 #define SZG_AERIAL_H 32u
 #define SZG_AERIAL_D 32u

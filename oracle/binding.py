@@ -46,6 +46,8 @@ def _load(name):
         h.oracle_composite.argtypes = [P(abi.SceneTexture), abi.Rect, P(abi.RowTile), P(abi.GBuffer), P(abi.ShadowMaps),
                                        P(abi.AtmospherePacked), U32, P(abi.CameraPacked), U32, P(abi.DirectionalLightPacked),
                                        U32, FP, U32, U32, FP, U32, U32, C.c_int]
+        h.oracle_composite_fast.argtypes = h.oracle_composite.argtypes[:-1] + [FP, U32, U32, U32, C.c_float, C.c_int]
+        h.oracle_aerial_sample.argtypes = [FP, U32, U32, U32, C.c_float, FP, FP, FP, C.c_size_t, FP]
         h.oracle_gbuffer_fill.argtypes = [P(abi.SceneTexture), abi.Rect, P(abi.RowTile), P(abi.GBuffer), P(abi.CameraPacked),
                                           U32, P(abi.FillScene), C.c_int]
         h.oracle_shadow_map.argtypes = [P(abi.Mat4), P(abi.Mat4), U32, P(abi.FillScene), FP, C.c_int]
@@ -230,12 +232,23 @@ def lights(frame, draw_rect, tile, shadow_maps, cam_packed, dir_lights, dir_coun
                         C.cast(spot_lights, P(abi.SpotLightPacked)) if spot_count else None, spot_count, threads)
 
 
-def composite(frame, draw_rect, tile, shadow_maps, atm_packed, cam_packed, dir_lights, sun_index, tlut, slut, threads=1):
+def composite(frame, draw_rect, tile, shadow_maps, atm_packed, cam_packed, dir_lights, sun_index, tlut, slut, threads=1,
+              aerial=None, dims=(32, 32, 32)):
+    """The composite; with aerial=(luminance volume [D * H, W, 4], max_distance) the fast composite of abi.h, which takes the
+    geometry pixels' aerial perspective from that host volume by the stated fetch."""
     g, st = frame.gbuffer(), frame.scene()
-    lib().oracle_composite(C.byref(st), draw_rect, C.byref(tile) if tile is not None else None, C.byref(g),
-                           C.byref(shadow_maps) if shadow_maps is not None else None, C.byref(atm_packed), 0,
-                           C.byref(cam_packed), 0, C.cast(dir_lights, P(abi.DirectionalLightPacked)), sun_index, fptr(tlut),
-                           tlut.shape[1], tlut.shape[0], fptr(slut), slut.shape[1], slut.shape[0], threads)
+    common = (C.byref(st), draw_rect, C.byref(tile) if tile is not None else None, C.byref(g),
+              C.byref(shadow_maps) if shadow_maps is not None else None, C.byref(atm_packed), 0,
+              C.byref(cam_packed), 0, C.cast(dir_lights, P(abi.DirectionalLightPacked)), sun_index, fptr(tlut),
+              tlut.shape[1], tlut.shape[0], fptr(slut), slut.shape[1], slut.shape[0])
+    if aerial is None:
+        lib().oracle_composite(*common, threads)
+        return
+    lum, max_distance = aerial
+    W, H, D = dims
+    lum = np.ascontiguousarray(lum, np.float32)
+    assert lum.size == W * H * D * 4
+    lib().oracle_composite_fast(*common, fptr(lum), W, H, D, float(max_distance), threads)
 
 
 def oetf(color_u16, function):
@@ -252,6 +265,19 @@ def aerial_lut(atm_packed, cam_packed, tlut, max_distance, dims=(32, 32, 32), th
     lib().oracle_aerial_lut(C.byref(atm_packed), 0, C.byref(cam_packed), 0, fptr(tlut), tlut.shape[1], tlut.shape[0], W, H, D,
                             max_distance, fptr(lum), fptr(tr), threads)
     return lum, tr
+
+
+def aerial_sample(lum, max_distance, sx, sy, dist, dims=(32, 32, 32)):
+    """The fast composite's fetch alone (abi.h): [n, 3] values of the host volume `lum` at screen positions (sx, sy) and
+    distances `dist`."""
+    W, H, D = dims
+    lum = np.ascontiguousarray(lum, np.float32)
+    assert lum.size == W * H * D * 4
+    sx, sy, dist = (np.ascontiguousarray(a, np.float32).ravel() for a in (sx, sy, dist))
+    assert sx.size == sy.size == dist.size
+    out = np.empty((sx.size, 3), np.float32)
+    lib().oracle_aerial_sample(fptr(lum), W, H, D, float(max_distance), fptr(sx), fptr(sy), fptr(dist), sx.size, fptr(out))
+    return out
 
 
 def multiscatter_lut(atm_packed, tlut, dim=32):

@@ -1039,12 +1039,41 @@ vec3 computeLightContribution(const IncomingLight& light, const PBRTexel& materi
 // ----------------------------------------------------------------------------
 // atmosphere/camera.comp:70-301
 // ----------------------------------------------------------------------------
+// The aerial-perspective luminance volume of the fast composite (include/szg/abi.h): W x (H * D) RGBA32F texels, slice k in
+// rows [k * H, (k + 1) * H).
+struct AerialVolume
+{
+    const float* luminance;
+    uint32_t W, H, D;
+    float maxDistance;
+};
+
 struct CompositeContext
 {
     Atmosphere atmosphere;
     TransmittanceLUT transmittance_LUT;
     Image skyview_LUT;
+    const AerialVolume* aerial = nullptr; // the fast composite: the geometry pixels' march is replaced by sampleAerial
 };
+
+// The fetch of the fast composite, operation by operation as include/szg/abi.h states it ("THE FETCH of the fast composite").
+// Only the two bilinear taps contain contraction sites (sample_linear_rgb: SZG_C_TEXCOORD, SZG_C_BILINEAR).
+vec3 sampleAerial(const AerialVolume& A, float sx, float sy, float dist)
+{
+    float const depth = (float)A.D;
+    float const fz = dist / A.maxDistance * depth - 0.5f;
+    float const ramp = fz < 0.0f ? fmaxf(dist / (0.5f * A.maxDistance / depth), 0.0f) : 1.0f;
+    float const z = fminf(fmaxf(fz, 0.0f), depth - 1.0f); // fmaxf(NaN, 0) = 0: z is a number in [0, D - 1]
+    int const k0 = (int)floorf(z);
+    int const k1 = std::min(k0 + 1, (int)A.D - 1);
+    float const wz = z - (float)k0;
+    size_t const slice = (size_t)A.W * A.H * 4u;
+    Image const s0{(const uint8_t*)(A.luminance + (size_t)k0 * slice), A.W, A.H, A.W * 16u};
+    Image const s1{(const uint8_t*)(A.luminance + (size_t)k1 * slice), A.W, A.H, A.W * 16u};
+    vec3 const l0 = sample_linear_rgb(s0, vec2{sx, sy});
+    vec3 const l1 = sample_linear_rgb(s1, vec2{sx, sy});
+    return (l0 * (1.0f - wz) + l1 * wz) * ramp;
+}
 
 // camera.comp:70-121
 vec3 sampleMap_Direction(const CompositeContext& c, vec3 position, vec3 direction)
@@ -1145,8 +1174,9 @@ vec3 sampleGround(const CompositeContext& c, vec3 origin, vec3 direction, float 
 }
 
 // camera.comp:237-278
+// `screen`: the pixel's (x / drawWidth, globalRow / drawHeight), read by the fast composite only
 vec3 computeGeometryLuminanceTransfer(const CompositeContext& c, vec3 origin, vec3 direction, const PBRTexel& material,
-                                      float shadowFactor)
+                                      float shadowFactor, vec2 screen)
 {
     const Atmosphere& atmosphere = c.atmosphere;
     vec3 const surfacePosition = material.position;
@@ -1166,7 +1196,8 @@ vec3 computeGeometryLuminanceTransfer(const CompositeContext& c, vec3 origin, ve
                                  clampf(dot(material.normal, lightDirection), 0.0f, 1.0f);
     float const distanceToGround = length(surfacePosition - origin);
     vec3 const aerialPerspectiveLuminance =
-        computeLuminanceScatteringIntegral(atmosphere, c.transmittance_LUT, origin, direction, distanceToGround);
+        c.aerial != nullptr ? sampleAerial(*c.aerial, screen.x, screen.y, distanceToGround)
+                            : computeLuminanceScatteringIntegral(atmosphere, c.transmittance_LUT, origin, direction, distanceToGround);
     return surfaceTransfer + aerialPerspectiveLuminance;
 }
 
@@ -1404,15 +1435,19 @@ void oracle_lights(const szg_scene_texture* scene, szg_rect drawRect, const szg_
     });
 }
 
-// atmosphere/camera.comp:303-395
-void oracle_composite(const szg_scene_texture* scene, szg_rect drawRect, const szg_rowtile* tile, const szg_gbuffer* gbuffer,
-                      const szg_shadowmaps* shadowMaps, const szg_atmosphere_packed* atmospheres, uint32_t atmosphereIndex,
-                      const szg_camera_packed* cameras, uint32_t cameraIndex,
-                      const szg_directional_light_packed* directionalLights, uint32_t sunLightIndex,
-                      const float* transmittanceLUT, uint32_t tWidth, uint32_t tHeight, const float* skyviewLUT,
-                      uint32_t sWidth, uint32_t sHeight, int threads)
+} // extern "C"
+
+namespace
+{
+// atmosphere/camera.comp:303-395; with `aerial` the fast composite of include/szg/abi.h (the same code, one term replaced)
+void composite(const szg_scene_texture* scene, szg_rect drawRect, const szg_rowtile* tile, const szg_gbuffer* gbuffer,
+               const szg_shadowmaps* shadowMaps, const szg_atmosphere_packed* atmospheres, uint32_t atmosphereIndex,
+               const szg_camera_packed* cameras, uint32_t cameraIndex, const szg_directional_light_packed* directionalLights,
+               uint32_t sunLightIndex, const float* transmittanceLUT, uint32_t tWidth, uint32_t tHeight, const float* skyviewLUT,
+               uint32_t sWidth, uint32_t sHeight, const AerialVolume* aerial, int threads)
 {
     CompositeContext c;
+    c.aerial = aerial;
     c.atmosphere = load(atmospheres[atmosphereIndex]);
     c.transmittance_LUT = {{(const uint8_t*)transmittanceLUT, tWidth, tHeight, tWidth * 16u}, (int)tWidth, (int)tHeight};
     c.skyview_LUT = {(const uint8_t*)skyviewLUT, sWidth, sHeight, sWidth * 16u};
@@ -1480,7 +1515,8 @@ void oracle_composite(const szg_scene_texture* scene, szg_rect drawRect, const s
                     material.position.y += atmosphere.planetRadiusMm;
 
                     sunIlluminanceToSkyLuminanceTransfer +=
-                        computeGeometryLuminanceTransfer(c, position, direction, material, surfaceSunShadowFactor);
+                        computeGeometryLuminanceTransfer(c, position, direction, material, surfaceSunShadowFactor,
+                                                         vec2{(float)x / (float)drawRect.width, (float)gy / (float)drawRect.height});
 
                     vec3 const transmittanceToSurface =
                         sampleTransmittanceLUT_Segment(c.transmittance_LUT, atmosphere, position, material.position);
@@ -1497,6 +1533,51 @@ void oracle_composite(const szg_scene_texture* scene, szg_rect drawRect, const s
             }
         }
     });
+}
+} // namespace
+
+extern "C" {
+
+void oracle_composite(const szg_scene_texture* scene, szg_rect drawRect, const szg_rowtile* tile, const szg_gbuffer* gbuffer,
+                      const szg_shadowmaps* shadowMaps, const szg_atmosphere_packed* atmospheres, uint32_t atmosphereIndex,
+                      const szg_camera_packed* cameras, uint32_t cameraIndex,
+                      const szg_directional_light_packed* directionalLights, uint32_t sunLightIndex,
+                      const float* transmittanceLUT, uint32_t tWidth, uint32_t tHeight, const float* skyviewLUT,
+                      uint32_t sWidth, uint32_t sHeight, int threads)
+{
+    composite(scene, drawRect, tile, gbuffer, shadowMaps, atmospheres, atmosphereIndex, cameras, cameraIndex, directionalLights,
+              sunLightIndex, transmittanceLUT, tWidth, tHeight, skyviewLUT, sWidth, sHeight, nullptr, threads);
+}
+
+// szg_skyview_record_composite_fast (include/szg/abi.h): oracle_composite with the aerial-perspective march of
+// computeGeometryLuminanceTransfer replaced by the stated fetch of a HOST volume (W x H x D froxels, RGBA32F, slice-major).
+// Sky pixels, the surface term and the reflection term with its own march are the exact composite's.
+void oracle_composite_fast(const szg_scene_texture* scene, szg_rect drawRect, const szg_rowtile* tile, const szg_gbuffer* gbuffer,
+                           const szg_shadowmaps* shadowMaps, const szg_atmosphere_packed* atmospheres, uint32_t atmosphereIndex,
+                           const szg_camera_packed* cameras, uint32_t cameraIndex,
+                           const szg_directional_light_packed* directionalLights, uint32_t sunLightIndex,
+                           const float* transmittanceLUT, uint32_t tWidth, uint32_t tHeight, const float* skyviewLUT,
+                           uint32_t sWidth, uint32_t sHeight, const float* aerialLuminance, uint32_t W, uint32_t H, uint32_t D,
+                           float maxDistance, int threads)
+{
+    AerialVolume const aerial{aerialLuminance, W, H, D, maxDistance};
+    composite(scene, drawRect, tile, gbuffer, shadowMaps, atmospheres, atmosphereIndex, cameras, cameraIndex, directionalLights,
+              sunLightIndex, transmittanceLUT, tWidth, tHeight, skyviewLUT, sWidth, sHeight, &aerial, threads);
+}
+
+// The fetch alone: out[3 i + c] = sampleAerial(volume, sx[i], sy[i], dist[i]). sx and sy are finite screen coordinates (the
+// composite passes x / width and row / height, in [0, 1)); dist is any binary32 value.
+void oracle_aerial_sample(const float* volume, uint32_t W, uint32_t H, uint32_t D, float maxDistance, const float* sx,
+                          const float* sy, const float* dist, size_t n, float* out)
+{
+    AerialVolume const aerial{volume, W, H, D, maxDistance};
+    for (size_t i = 0; i < n; i++)
+    {
+        vec3 const v = sampleAerial(aerial, sx[i], sy[i], dist[i]);
+        out[3 * i + 0] = v.x;
+        out[3 * i + 1] = v.y;
+        out[3 * i + 2] = v.z;
+    }
 }
 
 // Synthetic G-buffer fill (stands in for deferred/offscreen.vert:41-56 +

@@ -366,8 +366,9 @@ def test_composite(gpu, shape, fast):
 
     tight = tight_run(record)
     if fast:
-        # The fast mode is approximate by design and has no oracle: its tight run is pinned to the EXACT composite's tight run
-        # (which the other half of this test pins to the oracle) with the bounds of test_fast_composite_is_close_to_the_exact_one.
+        # The fast mode is approximate by design: its tight run is held to the EXACT composite's tight run (which the other half of
+        # this test pins to the oracle) with the bounds of test_fast_composite_is_close_to_the_exact_one. Bit for bit it is
+        # pinned to the oracle's fast composite by tests/test_gpu_fast_composite.py.
         a, b = tight_run(sky.recordComposite)["debug_color"], tight["debug_color"]
         geo = depth > 0
         assert (a[~geo].view(np.uint32) == b[~geo].view(np.uint32)).all(), "sky pixels must be untouched by the fast mode"
@@ -376,7 +377,7 @@ def test_composite(gpu, shape, fast):
             print(f"fast composite vs exact at {W}x{H}: max rel {rel.max():.3e}, mean rel {rel.mean():.3e} over {geo.sum()} geometry pixels")
             assert rel.max() < 5e-2 and rel.mean() < 5e-3
     deferred.cleanup()
-    if not fast:  # test_composite_matches_oracle / test_composite_with_sun_shadow_map (the fast mode has no oracle: approximate by design)
+    if not fast:  # test_composite_matches_oracle / test_composite_with_sun_shadow_map (the fast mode: tests/test_gpu_fast_composite.py)
         images = (abi.Image * 1)(gpu.ob.host_image(sun_map, abi.SZG_FORMAT_D32_SFLOAT))
         gpu.ob.composite(frame, inp.rect, None, abi.ShadowMaps(1, 0, C.cast(images, C.POINTER(abi.Image))), inp.atm, inp.cam, inp.dirs, 0,
                          tlut, slut, threads=8)

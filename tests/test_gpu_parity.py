@@ -364,7 +364,11 @@ def test_lights_linearity(gpu):
 # composite on identical LUTs / G-buffer / prior colour
 # ---------------------------------------------------------------------------
 def run_composite_case(gpu, W, H, elevation, spots=8, sun_shadow=None, tile=None, camera=None, lut=((512, 128), (256, 128)),
-                       poison=None):
+                       poison=None, aerial=None):
+    """aerial=(max_distance, volume or None): the FAST composite (abi.h) on both sides. The aerial LUT is recorded on the GPU
+    at max_distance; with volume=None it is downloaded and the oracle fetches from that download, otherwise `volume`
+    ([32 * 32, 32, 4] float32) is uploaded over the recorded one and handed to the oracle. frame.aerial_volume is the volume
+    both sides used."""
     inp = util.Inputs(W, H, elevation_degrees=elevation, spots=spots, camera=camera)
     cameras, atmospheres, lights = staged(gpu, inp)
     rows = H if tile is None else tile.local_rows
@@ -382,7 +386,8 @@ def run_composite_case(gpu, W, H, elevation, spots=8, sun_shadow=None, tile=None
     if sun_shadow is not None:
         images[0] = gpu.ob.host_image(sun_shadow, gpu.abi.SZG_FORMAT_D32_SFLOAT)
         shadow_host = gpu.abi.ShadowMaps(1, 0, C.cast(images, C.POINTER(gpu.abi.Image)))
-    gpu.ob.composite(frame, inp.rect, tile, shadow_host, inp.atm, inp.cam, inp.dirs, 0, tlut, slut, threads=8)
+    if aerial is None:
+        gpu.ob.composite(frame, inp.rect, tile, shadow_host, inp.atm, inp.cam, inp.dirs, 0, tlut, slut, threads=8)
 
     target = gpu.pl.SceneTexture(W, rows, debug=True)
     target.color.copy_(torch.from_numpy(prior.view(np.int16)))
@@ -396,8 +401,22 @@ def run_composite_case(gpu, W, H, elevation, spots=8, sun_shadow=None, tile=None
     sky = gpu.pl.SkyViewComputePipeline.create(transmittance_extent=(tw, th), skyview_extent=(sw, sh))
     sky.upload_lut(sky.transmittanceLUT(), tlut)
     sky.upload_lut(sky.skyviewLUT(), slut)
-    sky.recordComposite(None, target, inp.rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights,
-                        tile=tile)
+    record = sky.recordComposite
+    if aerial is not None:
+        max_distance, volume = aerial
+        sky.recordAerialLUT(None, 0, atmospheres, 0, cameras, max_distance)  # (sets the max distance the fast composite uses)
+        torch.cuda.synchronize()
+        lum_im, _ = sky.aerialLUT()
+        if volume is None:
+            volume = sky.download_lut(lum_im)
+        else:
+            sky.upload_lut(lum_im, volume)
+            torch.cuda.synchronize()
+        frame.aerial_volume = volume
+        gpu.ob.composite(frame, inp.rect, tile, shadow_host, inp.atm, inp.cam, inp.dirs, 0, tlut, slut, threads=8,
+                         aerial=(volume, max_distance))
+        record = sky.recordCompositeFast
+    record(None, target, inp.rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights, tile=tile)
     torch.cuda.synchronize()
     got = target.debug.cpu().numpy()
     got_q = target.color_numpy()
@@ -842,6 +861,15 @@ def test_fast_composite_is_close_to_the_exact_one(gpu):
         sky.recordCompositeFast(None, fast_t, inp.rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     sky.recordAerialLUT(None, 0, atmospheres, 0, cameras, 10.0e-3)  # 10 km
     sky.recordComposite(None, exact_t, inp.rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
+    torch.cuda.synchronize()
+    # what the fast composite is about to read, for the oracle: G-buffer, depth, the lights pass's colour, the three LUTs
+    frame = gpu.ob.HostFrame(W, H)
+    for name, plane in deferred.download_gbuffer(W, H).items():
+        frame.planes()[name][:] = plane
+    frame.depth[:] = fast_t.depth.cpu().numpy()
+    frame.color[:] = fast_t.color_numpy()
+    tlut, slut = sky.download_lut(sky.transmittanceLUT()), sky.download_lut(sky.skyviewLUT())
+    volume = sky.download_lut(sky.aerialLUT()[0])
     sky.recordCompositeFast(None, fast_t, inp.rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     torch.cuda.synchronize()
     a, b = exact_t.debug.cpu().numpy(), fast_t.debug.cpu().numpy()
@@ -850,6 +878,10 @@ def test_fast_composite_is_close_to_the_exact_one(gpu):
     rel = util.rel_err(a[geo][:, :3], b[geo][:, :3], util.ATOL_COLOR)
     print(f"fast composite vs exact: max rel {rel.max():.3e}, mean rel {rel.mean():.3e} over {geo.sum()} geometry pixels")
     assert rel.max() < 5e-2 and rel.mean() < 5e-3
+    # ... and it is the stated fetch (abi.h) of the recorded volume: the oracle's fast composite on the same inputs
+    gpu.ob.composite(frame, inp.rect, None, None, inp.atm, inp.cam, inp.dirs, 0, tlut, slut, threads=8, aerial=(volume, 10.0e-3))
+    assert_close(b, frame.debug, what="fast composite against the oracle's")
+    assert np.abs(fast_t.color_numpy().astype(np.int32) - frame.color.astype(np.int32)).max() <= 1
     deferred.cleanup()
     sky.destroy()
 
