@@ -11,15 +11,22 @@
     --present WxH[:format]: the blit onto a swapchain-sized image   editor.cpp:355-361 (szg/present.h), on the GPU
     --pipeline compute-collection[:NAME]: the editor's other        renderer.cpp:431-438 (szg/compute_collection.h)
       rendering pipeline instead of the deferred one
+    --ui-layer: the UI draw between the scene and the OETF          editor.cpp:720-748, uilayer.cpp:513-572 (szg/ui_layer.h)
 
     python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm [--debug-lines [--line-width 2]]
                                   [--present 1280x720[:rgba8|bgra8|a2b10g10r10]]
                                   [--pipeline compute-collection[:booleanpush|gradient_color|sparse_push_constant|matrix_color]]
+                                  [--ui-layer]
 
 --pipeline mirrors the editor's "Deferred" / "Compute Collection" switch (ui/engineui.cpp:19-22). With compute-collection
 the frame uploads and fills the debug-line list as before, then records ONE program of the collection over the scene colour
 (default gradient_color) with a visible block (abi.COMPUTE_COLLECTION_EXAMPLE_VALUES): no shadow, G-buffer, light, atmosphere
 or debug-line launches. The OETF and --present follow as in the editor.
+
+--ui-layer builds the frame the way the editor does: the renderer draws into UILayer::sceneTexture() at the extent of the scene
+viewport window, a draw list made with syzygy_amd.ui (a title bar, the scene viewport quad at the editor's UVs, a translucent
+side panel, a frame-time graph of filled rectangles) is drawn by UILayer::recordDraw into the output texture, and the OETF,
+--present and --out work on that OUTPUT image, as Editor::endFrame does.
 
 Without --present the 16-bit scene colour is copied to the host and the PPM holds its high bytes; with it every frame ends
 with the reference's LINEAR blit onto a WxH image of the given swapchain format (default rgba8) and the PPM is that image
@@ -56,11 +63,13 @@ def main(argv=None):
     ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
                     help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
                          "(default), reference (the reference sampler's 1.0) or a number")
+    ap.add_argument("--ui-layer", action="store_true",
+                    help="draw an editor-like UI frame over the scene (szg/ui_layer.h) and present the UI output texture")
     args = ap.parse_args(argv)
 
     import torch
 
-    from syzygy_amd import abi, lib, meshes, pipelines as pl, scene
+    from syzygy_amd import abi, lib, meshes, pipelines as pl, scene, ui
 
     W, H = args.width, args.height
     try:
@@ -107,10 +116,19 @@ def main(argv=None):
     cameras = pl.TStagedBuffer(abi.CameraPacked, 1)
     atmospheres = pl.TStagedBuffer(abi.AtmospherePacked, 1)
     lights = pl.TStagedBuffer(abi.DirectionalLightPacked, 2)
-    target = pl.SceneTexture(W, H)
+    ui_layer = None
+    if args.ui_layer:  # UILayer::create at the window's extent: scene and output texture, the scene texture registered with ImGui
+        ui_layer = pl.UILayer.create((W, H))
+        white = ui_layer.addTexture(torch.full((1, 1, 4), 255, dtype=torch.uint8, device="cuda"))  # the font atlas's white texel
+        panel_w, title_h = max(W // 5, 8), 22
+        view_min = (panel_w + 6, title_h + 6)
+        ui_layer.setSceneViewportExtent(W - view_min[0] - 6, H - view_min[1] - 6)  # the "Scene Viewport" window's content
+        frame_times = []
+    target = ui_layer.sceneTexture() if ui_layer else pl.SceneTexture(W, H)
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=len(spots), max_shadow_maps=2 + len(spots), shadow_map_dim=args.shadow_map)
     sky = pl.SkyViewComputePipeline.create()
-    rect = pl.rect(W, H)
+    rect = ui_layer.sceneViewport().renderedSubregion if ui_layer else pl.rect(W, H)  # editor.cpp:720-735: the viewport's subregion
+    RW, RH = rect.width, rect.height
     debug_lines = pl.DebugLines()  # Renderer::m_debugLines, DEBUGLINES_CAPACITY vertices (renderer.hpp:103)
     debug_lines.enabled, debug_lines.lineWidth = args.debug_lines, args.line_width
     try:
@@ -124,6 +142,7 @@ def main(argv=None):
         collection.selectShaderByName(shader)
         collection.writeExampleValues()
 
+    presented = target
     t_start = time.perf_counter()
     elapsed, dt = 0.0, 1.0 / 60.0
     for frame in range(args.frames):
@@ -144,7 +163,7 @@ def main(argv=None):
         atm, sun, moon = scene.atmosphere_baked(atmosphere, bounds)
 
         # Renderer::recordDraw
-        for buf, items in ((cameras, [scene.camera_packed(camera, W / H)]), (atmospheres, [atm]), (lights, [sun, moon])):
+        for buf, items in ((cameras, [scene.camera_packed(camera, RW / RH)]), (atmospheres, [atm]), (lights, [sun, moon])):
             buf.clearStaged()
             buf.push(items)
             buf.recordCopyToDevice()
@@ -157,13 +176,28 @@ def main(argv=None):
             sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
             debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423
             debug_lines.recordDraw(None, 0, target, rect, cameras)  # renderer.cpp:425-427, :445-476 (only when enabled)
-        pl.recordOETF(None, target, W, H)
-        if present:  # editor.cpp:355-361: the whole scene onto the whole swapchain image, LINEAR
-            pl.record_copy_image_to_image(None, target, swapchain, dstFormat=present[2])
+        presented = target
+        if ui_layer:  # editor.cpp:736-748: the UI draw, then endFrame on uiOutput.texture
+            frame_times = (frame_times + [4.0 + 10.0 * abs(np.sin(0.37 * frame))])[-60:]
+            dl = ui.DrawList(white)
+            dl.add_rect_filled((0, 0), (W, title_h), ui.col32(41, 74, 122, 255))  # title bar
+            uv_min, uv_max = ui_layer.sceneViewportUV()
+            dl.add_image(ui_layer.sceneTextureHandle(), view_min, (view_min[0] + RW, view_min[1] + RH), uv_min, uv_max)
+            dl.push_clip_rect((0, title_h), (panel_w, H), True)
+            dl.add_rect_filled((0, title_h), (panel_w, H), ui.col32(20, 20, 24, 230))  # side panel
+            bar_w = (panel_w - 16) / 60.0
+            for i, ms in enumerate(frame_times):  # frame-time graph
+                x = 8 + i * bar_w
+                dl.add_rect_filled((x, H - 12 - 4.0 * ms), (x + bar_w * 0.8, H - 12), ui.col32(230, 180, 60, 200))
+            dl.pop_clip_rect()
+            presented = ui_layer.recordDraw(None, ui.DrawData((0, 0), (W, H), (1, 1), [dl])).texture
+        pl.recordOETF(None, presented, W, H)
+        if present:  # editor.cpp:355-361: the whole presented image onto the whole swapchain image, LINEAR
+            pl.record_copy_image_to_image(None, presented, swapchain, dstFormat=present[2])
         elapsed += dt
     torch.cuda.synchronize()
     wall = time.perf_counter() - t_start
-    image = target.color_numpy()
+    image = presented.color_numpy()
     print(f"{args.frames} frames of {W}x{H}: {wall / args.frames * 1e3:.2f} ms per frame including host scene prep; "
           f"mean display value {image[..., :3].mean() / 65535.0:.3f}")
     if args.out and present:
@@ -176,6 +210,8 @@ def main(argv=None):
         print("wrote", args.out)
     if args.debug_lines:
         print(f"debug lines: {debug_lines.lastFrameDrawResults.verticesDrawn // 2} lines, width {debug_lines.lineWidth}")
+    if ui_layer:
+        ui_layer.cleanup()
     debug_lines.cleanup()
     deferred.cleanup()
     sky.destroy()

@@ -16,6 +16,7 @@
 //   recordCopyImageToImage      imageoperations.cpp:45-176 szg::recordCopyImageToImage (szg/present.h)
 //   Editor::endFrame's tail     editor.cpp:303-361         szg::recordPresent
 //   ComputeCollectionPipeline   pipelines.hpp:166-235      szg::ComputeCollectionPipeline (szg/compute_collection.h)
+//   UILayer                     editor/uilayer.hpp:36-114  szg::UILayer (szg/ui_layer.hpp, included at the end; szg/ui_layer.h)
 //   std::span<MeshInstanced const> sceneGeometry           szg_fill_scene const* (synthetic)
 //
 // Error behaviour follows the reference: construction failures give an invalid object /
@@ -654,3 +655,6 @@ struct ComputeCollectionPipeline
     mutable int m_lastStatus{SZG_OK};
 };
 } // namespace szg
+
+// UILayer (editor/uilayer.hpp): builds on SceneTexture, TStagedBuffer and detail::note above
+#include "szg/ui_layer.hpp"

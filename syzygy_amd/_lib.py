@@ -67,6 +67,12 @@ def lib():
             # a library named explicitly for a comparison (tools/bench_raster_libraries.py --baseline: a parent commit's build)
             # may predate the header: everything else works, and a mip entry point raises AttributeError when it is called
             print(f"[szg] {path} predates include/szg/mipmaps.h ({e}): mip-mapped textures are unavailable with it", file=sys.stderr)
+        try:
+            abi.bind(handle, abi.UI_LAYER_FUNCTIONS)
+        except AttributeError as e:
+            if "SZG_HIP_LIBRARY" not in os.environ:
+                raise RuntimeError(f"{path} predates include/szg/ui_layer.h ({e}); rebuild the library") from e
+            print(f"[szg] {path} predates include/szg/ui_layer.h ({e}): the UI layer pass is unavailable with it", file=sys.stderr)
         _LIB = handle
     return _LIB
 

@@ -608,6 +608,46 @@ MIPMAP_FUNCTIONS = {
     "szg_deferred_set_texture_mips": (C.c_int, [VP, P(TextureMips), U32, C.c_float]),
 }
 
+# include/szg/ui_layer.h
+SZG_UI_ADDRESS_REPEAT = 0
+SZG_UI_ADDRESS_CLAMP_TO_EDGE = 2
+SZG_UI_ADDRESS_CLAMP_TO_BORDER = 3
+SZG_UI_LOAD_OP_LOAD = 0
+SZG_UI_LOAD_OP_CLEAR = 1
+SZG_UI_GUARD_BAND = 1048576.0
+SZG_UI_MAX_TRIANGLE_CAPACITY = 1 << 24
+SZG_UI_MAX_COMMAND_CAPACITY = 1 << 20
+
+
+class UIDrawVert(C.Structure):
+    """ImDrawVert"""
+    _fields_ = [("pos", C.c_float * 2), ("uv", C.c_float * 2), ("col", U32)]
+
+
+class UISampler(C.Structure):
+    _fields_ = [("filter", U32), ("address", U32)]
+
+
+class UIDrawCmd(C.Structure):
+    """ImDrawCmd with global offsets; `texture` is a handle of szg_ui_layer_add_texture"""
+    _fields_ = [("clip_rect", C.c_float * 4), ("texture", VP), ("vtx_offset", U32), ("idx_offset", U32), ("elem_count", U32),
+                ("reserved", U32)]
+
+
+class UIDrawData(C.Structure):
+    _fields_ = [("display_pos", C.c_float * 2), ("display_size", C.c_float * 2), ("framebuffer_scale", C.c_float * 2),
+                ("d_vertices", VP), ("vertex_count", U32), ("d_indices", VP), ("index_count", U32),
+                ("commands", P(UIDrawCmd)), ("command_count", U32)]
+
+
+UI_LAYER_FUNCTIONS = {
+    "szg_ui_layer_create": (C.c_int, [P(VP), U32, U32, C.c_int]),
+    "szg_ui_layer_destroy": (None, [VP]),
+    "szg_ui_layer_add_texture": (C.c_int, [VP, P(Image), UISampler, P(VP)]),
+    "szg_ui_layer_remove_texture": (C.c_int, [VP, VP]),
+    "szg_ui_layer_record_draw": (C.c_int, [VP, VP, P(Image), Rect, U32, P(C.c_float), P(UIDrawData)]),
+}
+
 
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""

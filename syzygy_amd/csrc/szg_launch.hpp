@@ -9,6 +9,7 @@
 #include "szg/debuglines.h"
 #include "szg/present.h"
 #include "szg/raster.h"
+#include "szg/ui_layer.h"
 
 namespace szg
 {
@@ -233,6 +234,57 @@ hipError_t launch_debug_lines(hipStream_t s, const szg_scene_texture& scene, uns
 // Arguments already validated; `table` is the OETF table of info.encode, or nullptr for SZG_PRESENT_ENCODE_NONE.
 hipError_t launch_present(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_present_info& info,
                           const unsigned short* table);
+
+// ---- UI layer pass (kernels_ui_layer.hip, include/szg/ui_layer.h) ----
+// One ImDrawCmd that can draw, as the host resolved it (api_ui_layer.cpp): the texture and sampler its handle names, the
+// pixel box scissor ∩ viewport ∩ render area ∩ image, and its triangles after ASSEMBLY's truncation. Read through scalar loads.
+struct UICommand
+{
+    const void* texData;
+    unsigned texWidth, texHeight, texPitch;
+    unsigned tex16;  // 0: RGBA8_UNORM, 1: RGBA16_UNORM
+    unsigned filter, address;
+    int clip[4];     // x0, y0, x1, y1 (exclusive)
+    unsigned vtxOffset, firstIndex, triCount;
+    unsigned firstTri; // submission-order number of the command's first triangle
+};
+static_assert(sizeof(UICommand) == 64, "UICommand layout");
+// One triangle after setup, sign-normalised (everything multiplied by s = sign(det)): the edge functions at the centre of
+// pixel (0, 0) and their steps per pixel, exact; which edges are left or top; the attributes, vertex i opposite edge i.
+struct UIPrim
+{
+    long long e0[3]; // s E_i at C = (128, 128)
+    long long ex[3]; // s E_i(px + 1, py) - s E_i(px, py) = 256 s a_i
+    long long ey[3]; // 256 s b_i
+    float det;       // float(|det|)
+    unsigned topLeft; // bit i: edge i owns its zero
+    unsigned command;
+    unsigned box[2]; // the pixel box, as in UILayerBuffers::boxes
+    unsigned pad;
+    float u[3], v[3], r[3], g[3], b[3], a[3];
+};
+static_assert(sizeof(UIPrim) == 168, "UIPrim layout");
+// Device scratch of one layer, sized at creation (api_ui_layer.cpp). A box is x: min | max << 16, y likewise, max exclusive;
+// the empty box is min = 0xFFFF, max = 0.
+struct UILayerBuffers
+{
+    UICommand* commands = nullptr; // [commandCapacity]
+    UIPrim* prims = nullptr;       // [triangleCapacity] submission order
+    uint2* boxes = nullptr;        // [triangleCapacity rounded up to 64]
+    uint2* chunkBoxes = nullptr;   // [boxes / 64, rounded up to 64]: 64 consecutive triangles
+    uint2* superBoxes = nullptr;   // [chunkBoxes / 64]: 64 consecutive chunks
+};
+struct UIDrawParams
+{
+    float displayPos[2], scale[2];
+    const szg_ui_draw_vert* vertices;
+    const uint16_t* indices;
+    unsigned vertexCount, commandCount, triCount;
+};
+// Arguments already validated. `area`: render area ∩ image, not empty. commands[0..commandCount) are in b.commands already
+// (uploaded on `s`).
+hipError_t launch_ui_layer(hipStream_t s, const szg_image& output, szg_rect area, bool clear, const float clearColor[4],
+                           const UIDrawParams& draw, const UILayerBuffers& b);
 
 // ---- compute-collection pipeline (kernels_compute_collection.hip, include/szg/compute_collection.h) ----
 // A push-constant block as the kernels take it, by value: the largest of the four (matrix_color), zero-filled behind the

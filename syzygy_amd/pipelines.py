@@ -10,6 +10,7 @@ Names, argument order and meaning follow the reference:
   DebugLineGraphicsPipeline renderer/pipelines.hpp:238-268
   record_copy_image_to_image / record_present   renderer/imageoperations.cpp:45-176, editor/editor.cpp:303-361
   ComputeCollectionPipeline renderer/pipelines.hpp:166-235, pipelines.cpp:223-368
+  UILayer                   editor/uilayer.hpp:36-114, uilayer.cpp:285-337, :412-450, :513-572 (the draw only: szg/ui_layer.h)
 with `cmd` (VkCommandBuffer) replaced by a HIP stream handle and Vulkan images by
 linear device buffers. torch is used only to own device memory and streams.
 """
@@ -19,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import abi
+from . import abi, ui
 from ._lib import check, lib
 
 
@@ -95,7 +96,7 @@ class TStagedBuffer:
         n = len(self._staged)
         size = C.sizeof(self.struct_type)
         if n:
-            raw = b"".join(bytes(v) for v in self._staged)
+            raw = self._stagedBytes()
             slot = self._ring_next
             self._ring_next = (slot + 1) % self.SLOTS
             if self._ring_done[slot] is not None:
@@ -110,6 +111,9 @@ class TStagedBuffer:
             self._ring_done[slot] = done
         self._device_size = n
         self._dirty = False
+
+    def _stagedBytes(self):
+        return b"".join(bytes(v) for v in self._staged)
 
     def deviceAddress(self):
         return self._device.data_ptr()
@@ -874,3 +878,137 @@ class DebugLines:
 
     def cleanup(self):
         self.pipeline.cleanup()
+
+
+# ---------------------------------------------------------------------------
+# UI layer pass (include/szg/ui_layer.h)
+# ---------------------------------------------------------------------------
+class TStagedArray(TStagedBuffer):
+    """A TStagedBuffer staged from one numpy array of records (an ImVector's Data / Size) instead of a list of structs."""
+
+    def __init__(self, dtype, capacity, device="cuda:0"):
+        self.dtype = np.dtype(dtype)
+        super().__init__(C.c_uint8 * self.dtype.itemsize, capacity, device)
+
+    def stage(self, values):
+        values = np.ascontiguousarray(values, self.dtype)
+        if len(values) > self.capacity:
+            raise ValueError("TStagedArray: staged size exceeds capacity")
+        self._staged = values
+        self._dirty = True
+
+    def push(self, value):
+        raise TypeError("TStagedArray is staged whole: stage(array)")
+
+    def _stagedBytes(self):
+        return self._staged.tobytes()
+
+
+SceneViewport = namedtuple("SceneViewport", "focused texture renderedSubregion")  # uilayer.hpp:23-28
+UIOutputImage = namedtuple("UIOutputImage", "texture renderedSubregion")  # uilayer.hpp:30-34
+
+
+class UILayer:
+    """uilayer.hpp:36-114, the part that is a render pass: the scene texture the renderer draws into, the output texture the
+    frame is presented from, the textures the draw data may name, and recordDraw. Widgets, layout and ImGui itself are out of
+    scope: the draw data comes from Dear ImGui in an engine, or from syzygy_amd.ui here.
+
+    create() allocates both textures at `textureCapacity` (uilayer.cpp:285-328) and registers the scene texture with its own
+    sampler, NEAREST / CLAMP_TO_BORDER with an opaque-black border (scenetexture.cpp:104-109, uilayer.cpp:318-322)."""
+
+    def __init__(self, textureCapacity, triangleCapacity=1 << 16, commandCapacity=4096, device="cuda:0", device_index=0):
+        w, h = (int(v) for v in textureCapacity)
+        handle = C.c_void_p()
+        check(lib().szg_ui_layer_create(C.byref(handle), int(triangleCapacity), int(commandCapacity), int(device_index)))
+        self._h = handle
+        self.triangleCapacity, self.commandCapacity = int(triangleCapacity), int(commandCapacity)
+        self._vertices = TStagedArray(ui.DRAW_VERT, 3 * self.triangleCapacity, device)
+        self._indices = TStagedArray(np.uint16, 3 * self.triangleCapacity, device)
+        self._keep = {}  # handle -> the tensor whose memory the texture names
+        self._scene = SceneTexture(w, h, device)
+        self._output = SceneTexture(w, h, device)
+        self._sceneHandle = self.addTexture(self._scene.color, abi.SZG_FILTER_NEAREST, abi.SZG_UI_ADDRESS_CLAMP_TO_BORDER)
+        self._viewport = abi.Rect(0, 0, w, h)
+
+    @classmethod
+    def create(cls, textureCapacity, **kwargs):
+        return cls(textureCapacity, **kwargs)
+
+    def sceneTexture(self):
+        return self._scene
+
+    def outputTexture(self):
+        return self._output
+
+    def sceneTextureHandle(self):
+        """m_imguiSceneTextureHandle: the ImTextureID of the scene viewport quad"""
+        return self._sceneHandle
+
+    def setSceneViewportExtent(self, width, height):
+        """What the "Scene Viewport" window (statelesswidgets.cpp:868-885) measures: the content extent the scene is rendered
+        at, clamped to the texture's capacity."""
+        self._viewport = abi.Rect(0, 0, min(int(width), self._scene.width), min(int(height), self._scene.height))
+
+    def sceneViewportUV(self):
+        """statelesswidgets.cpp:868-885: uv_max = contentExtent / textureCapacity of the viewport quad"""
+        return (0.0, 0.0), (self._viewport.width / self._scene.width, self._viewport.height / self._scene.height)
+
+    def sceneViewport(self, forceFocus=False):
+        """uilayer.cpp:412-448: {focused, texture, renderedSubregion}"""
+        return SceneViewport(bool(forceFocus), self._scene, self._viewport)
+
+    def addTexture(self, tensor, filter=abi.SZG_FILTER_LINEAR, address=abi.SZG_UI_ADDRESS_REPEAT):
+        """ImGui_ImplVulkan_AddTexture: `tensor` is uint8 [h, w, 4] (RGBA8_UNORM) or int16 / uint16 [h, w, 4] (RGBA16_UNORM);
+        returns the ImTextureID (an int) that draw commands name. The tensor is kept alive until removeTexture."""
+        fmt = abi.SZG_FORMAT_RGBA8_UNORM if tensor.dtype == torch.uint8 else abi.SZG_FORMAT_RGBA16_UNORM
+        if fmt == abi.SZG_FORMAT_RGBA16_UNORM and tensor.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise ValueError(f"a texture holds 8- or 16-bit codes, got {tensor.dtype}")
+        im = _strided_image(tensor, fmt, 4)
+        out = C.c_void_p()
+        check(lib().szg_ui_layer_add_texture(self._h, C.byref(im), abi.UISampler(int(filter), int(address)), C.byref(out)))
+        self._keep[out.value] = tensor
+        return out.value
+
+    def removeTexture(self, handle):
+        check(lib().szg_ui_layer_remove_texture(self._h, C.c_void_p(handle)))
+        self._keep.pop(handle, None)
+
+    def recordDraw(self, cmd, drawData, loadOp=abi.SZG_UI_LOAD_OP_CLEAR, clearColor=(0.0, 0.0, 0.0, 1.0)):
+        """uilayer.cpp:513-572: the render area is (int32)DisplayPos, (uint32)DisplaySize (:536-545), the output texture is
+        cleared to opaque black and the draw data drawn into it. `drawData`: a ui.DrawData (or what its flatten() returns).
+        Returns UIOutputImage{texture, renderedSubregion}: what Editor::endFrame presents."""
+        flat = drawData.flatten() if hasattr(drawData, "flatten") else drawData
+        area = abi.Rect(int(flat.display_pos[0]), int(flat.display_pos[1]), int(flat.display_size[0]), int(flat.display_size[1]))
+        self._vertices.stage(flat.vertices)
+        self._indices.stage(flat.indices)
+        self._vertices.recordCopyToDevice(cmd)
+        self._indices.recordCopyToDevice(cmd)
+        n = len(flat.commands)
+        commands = (abi.UIDrawCmd * max(n, 1))()
+        for dst, c in zip(commands, flat.commands):
+            dst.clip_rect[:] = [float(v) for v in c.clip_rect]
+            dst.texture = c.texture
+            dst.vtx_offset, dst.idx_offset, dst.elem_count = int(c.vtx_offset), int(c.idx_offset), int(c.elem_count)
+        dd = abi.UIDrawData()
+        dd.display_pos[:] = [float(v) for v in flat.display_pos]
+        dd.display_size[:] = [float(v) for v in flat.display_size]
+        dd.framebuffer_scale[:] = [float(v) for v in flat.framebuffer_scale]
+        dd.d_vertices, dd.vertex_count = self._vertices.deviceAddress(), len(flat.vertices)
+        dd.d_indices, dd.index_count = self._indices.deviceAddress(), len(flat.indices)
+        dd.commands, dd.command_count = commands, n
+        out = _strided_image(self._output.color, abi.SZG_FORMAT_RGBA16_UNORM, 4)
+        check(lib().szg_ui_layer_record_draw(self._h, _stream_handle(cmd), C.byref(out), area, int(loadOp), _f(clearColor, 4),
+                                             C.byref(dd)))
+        return UIOutputImage(self._output, area)
+
+    def cleanup(self):
+        if self._h:
+            lib().szg_ui_layer_destroy(self._h)
+            self._h = None
+            self._keep = {}
+
+    def __del__(self):
+        try:
+            self.cleanup()
+        except Exception:
+            pass
