@@ -222,6 +222,8 @@ def test_lights_match_oracle(gpu, spots, skip):
     worst = assert_close(got, frame.debug, what=f"lights spots={spots} skip={skip}")
     assert np.abs(got_q.astype(np.int32) - frame.color.astype(np.int32)).max() <= 1
     assert (got_q[..., 3] == 65535).all()
+    assert (got.view(np.uint32) == frame.debug.view(np.uint32)).all()  # README: the pass is bit-identical to the oracle
+    assert (got_q == frame.color).all()
     print(f"lights spots={spots} skip={skip}: worst/tol {worst:.3f}")
 
 
@@ -306,6 +308,8 @@ def test_lights_with_extreme_falloff_parameters(gpu):
 def test_lights_ragged_extent(gpu):
     got, got_q, frame = run_lights_case(gpu, 70, 37, 8, 1)
     assert_close(got, frame.debug, what="lights 70x37")
+    assert (got.view(np.uint32) == frame.debug.view(np.uint32)).all()
+    assert (got_q == frame.color).all()
 
 
 def test_lights_background_keeps_clear_colour(gpu):
@@ -324,6 +328,8 @@ def test_lights_with_shadow_maps(gpu):
     got, got_q, frame = run_lights_case(gpu, 160, 90, 8, 1, shadow=maps)
     assert_close(got, frame.debug, what="lights with shadow maps")
     assert np.abs(got_q.astype(np.int32) - frame.color.astype(np.int32)).max() <= 1
+    assert (got.view(np.uint32) == frame.debug.view(np.uint32)).all()
+    assert (got_q == frame.color).all()
 
 
 def test_lights_capacity_is_an_error(gpu):
