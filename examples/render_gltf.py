@@ -65,6 +65,9 @@ def main(argv=None):
     ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
                     help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
                          "(default), reference (the reference sampler's 1.0) or a number")
+    ap.add_argument("--jpeg", nargs="?", const="host", default=None, choices=("host", "device"), metavar="host|device",
+                    help="decode JPEG material maps (szg/jpeg.h; default: PNG only, as before): on the host, or the entropy decode on "
+                         "the host and IDCT, upsampling and colour conversion on the GPU")
     args = ap.parse_args(argv)
 
     import torch
@@ -84,7 +87,9 @@ def main(argv=None):
     if not path:
         path = os.path.join(tempfile.mkdtemp(), "sphere.glb")
         write_sphere(path)
-    asset = assets.load_gltf(path, abi.SZG_GLTF_DECODE_BUFFER_VIEW_IMAGES if args.embedded_images else 0)
+    flags = abi.SZG_GLTF_DECODE_BUFFER_VIEW_IMAGES if args.embedded_images else 0
+    flags |= {None: 0, "host": abi.SZG_GLTF_DECODE_JPEG, "device": abi.SZG_GLTF_JPEG_FOR_DEVICE}[args.jpeg]
+    asset = assets.load_gltf(path, flags)
     for line in asset.warnings:
         print("[warning]", line)
     print(f"{path}: {len(asset.meshes)} meshes, {len(asset.materials)} materials")

@@ -24,7 +24,7 @@
  * URIs are read from the glTF 2.0 specification. Of the two image encodings glTF 2.0 allows only PNG is decoded
  * (RFC 1951 / the PNG specification: bit depths 1-16, all colour types, tRNS, Adam7; 16-bit samples keep their high
  * byte and gamma chunks are ignored, as a 4-channel 8-bit request to the reference's decoder answers; checksums not
- * verified). JPEG is NOT decoded.
+ * verified). JPEG is NOT decoded by default; with SZG_GLTF_DECODE_JPEG or SZG_GLTF_JPEG_FOR_DEVICE (below, szg/jpeg.h) it is.
  * An image that is not decoded fails like any undecodable image does in the reference (warning, default map kept).
  * The reference holds no usable asset for this path (assets/sphere.glb is a 132-byte LFS pointer): parity unpinned;
  * tests write glTF/GLB/PNG files with an independent Python encoder and compare array by array, and decode PNG files
@@ -53,6 +53,15 @@ extern "C" {
  * "Unsupported glTF image source found." for images stored in a bufferView — which is how GLB files embed them.
  * Default: the same (the map stays the default one). With this flag such images are decoded too. */
 #define SZG_GLTF_DECODE_BUFFER_VIEW_IMAGES 1u
+
+/* szg/jpeg.h, opt-in. A glTF image that is a JPEG stream is decoded on the host (szg_jpeg_open + szg_jpeg_reconstruct_host)
+ * and then treated exactly like a decoded PNG, ORM overrides included. A stream that fails warns and keeps the default
+ * map, like any undecodable image; the "JPEG streams" summary line counts only images that were not decoded. */
+#define SZG_GLTF_DECODE_JPEG 2u
+/* Implies SZG_GLTF_DECODE_JPEG. Only the entropy decode happens on the host: for a map that is a JPEG stream,
+ * szg_asset_texture.rgba STAYS NULL (with the stream's width, height, srgb and name filled in) — NULL no longer means "the
+ * default map" for such a map; ask szg_gltf_material_jpeg. Maps that are PNG are decoded as always. */
+#define SZG_GLTF_JPEG_FOR_DEVICE 4u
 
 typedef struct szg_gltf szg_gltf; /* opaque; owns every array it hands out */
 

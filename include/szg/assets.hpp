@@ -10,7 +10,9 @@
 //   GPUMeshBuffers      renderer/buffers.hpp                    szg::GPUMeshBuffers (vertex + index arrays in device memory)
 //   Mesh                assets/assets.hpp:38-44                 szg::Mesh
 //   AssetLibrary        assets/assets.hpp:95-244                szg::AssetLibrary: loadDefaultAssets, loadGLTFFromPath,
-//                                                               loadTextureFromPath, defaultMesh, deduplicated names
+//                                                               loadTextureFromPath, defaultMesh, deduplicated names;
+//                                                               JPEG maps are opt-in (szg/jpeg.h: the SZG_GLTF_* flags of
+//                                                               loadGLTFFromPath, setDecodeJPEG for loadTextureFromPath)
 //   MeshInstanced       renderer/scene.hpp:109-147              szg::MeshInstanced: originals / transforms, models +
 //                                                               modelInverseTransposes staged buffers, setMesh,
 //                                                               material overrides
@@ -23,6 +25,8 @@
 
 #include <cstdio>
 #include <filesystem>
+#include <fstream>
+#include <iterator>
 #include <memory>
 #include <optional>
 #include <span>
@@ -31,6 +35,7 @@
 #include <vector>
 
 #include "szg/assets.h"
+#include "szg/jpeg.h"
 #include "szg/pipelines.hpp"
 
 namespace szg
@@ -81,30 +86,94 @@ struct ImageView
         view->height = height;
         view->srgb = srgb;
         view->name = std::move(name);
-        size_t const chainBytes = generateMips ? szg_mip_chain_bytes(width, height) : 0;
-        if (chainBytes > 0 && hipMalloc(&view->mipChain, chainBytes) == hipSuccess)
+        if (generateMips)
         {
-            szg_texture const level0 = view->texture();
-            if (szg_record_generate_mipmaps(nullptr, &level0, view->mipChain, chainBytes) == SZG_OK)
-            {
-                view->mipLevels = szg_mip_level_count(width, height);
-            }
-            else
-            {
-                (void)hipFree(view->mipChain);
-                view->mipChain = nullptr;
-            }
+            view->buildMips();
         }
-        if (chainBytes > 0 && view->mipLevels <= 1)
+        return view;
+    }
+
+    // szg/jpeg.h, the device path: the coefficient planes of an entropy-decoded stream are uploaded, the reconstruction
+    // (k_jpeg_idct, k_jpeg_color) is recorded on the null stream with the masks (texel & rgbaAnd) | rgbaOr, and the mip chain
+    // behind it on the same stream. The szg_jpeg is only read and not needed once this returns.
+    static auto uploadJPEG(szg_jpeg const* jpeg, uint32_t rgbaAnd, uint32_t rgbaOr, bool srgb, std::string name, bool generateMips = false)
+        -> std::shared_ptr<ImageView const>
+    {
+        szg_jpeg_frame frame{};
+        if (szg_jpeg_get_frame(jpeg, &frame) != SZG_OK)
         {
-            std::fprintf(stderr, "[szg] Failed to build the mip chain of image '%s'; it keeps one level.\n", view->name.c_str());
+            return nullptr;
         }
+        auto view = std::make_shared<ImageView>();
+        void* temporary[4] = {nullptr, nullptr, nullptr, nullptr}; // the device coefficients and the sample planes
+        auto const release = [&temporary] {
+            for (void* p : temporary)
+            {
+                (void)hipFree(p); // waits for the stream: the kernels have read them
+            }
+        };
+        bool ok = true;
+        for (uint32_t p = 0; p < frame.plane_count && ok; p++)
+        {
+            szg_jpeg_plane& plane = frame.planes[p];
+            temporary[p] = detail::uploadBytes(plane.coefficients, size_t{plane.blocks_w} * plane.blocks_h * 64 * sizeof(int16_t));
+            plane.coefficients = static_cast<int16_t const*>(temporary[p]);
+            ok = temporary[p] != nullptr;
+        }
+        size_t const scratchBytes = szg_jpeg_scratch_bytes(&frame);
+        ok = ok && scratchBytes > 0 && hipMalloc(&temporary[3], scratchBytes) == hipSuccess;
+        ok = ok && hipMalloc(&view->data, size_t{frame.width} * frame.height * 4) == hipSuccess;
+        if (ok)
+        {
+            szg_image const dst{view->data, frame.width, frame.height, frame.width * 4, SZG_FORMAT_RGBA8_UNORM};
+            ok = szg_record_jpeg_reconstruct(nullptr, &frame, temporary[3], scratchBytes, rgbaAnd, rgbaOr, &dst) == SZG_OK;
+        }
+        if (!ok)
+        {
+            release();
+            std::fprintf(stderr, "[szg] Failed to upload JPEG image to GPU.\n");
+            return nullptr;
+        }
+        view->width = frame.width;
+        view->height = frame.height;
+        view->srgb = srgb;
+        view->name = std::move(name);
+        if (generateMips)
+        {
+            view->buildMips();
+        }
+        release();
         return view;
     }
     [[nodiscard]] auto texture() const -> szg_texture { return szg_texture{data, width, height, width * 4, srgb ? 1u : 0u}; }
     // the entry of this image for DeferredShadingPipeline::setTextureMips
     [[nodiscard]] auto textureMips() const -> szg_texture_mips { return szg_texture_mips{data, mipChain, mipLevels}; }
 
+  private:
+    // the full chain of szg/mipmaps.h on the null stream, behind whatever wrote level 0 there
+    void buildMips()
+    {
+        size_t const chainBytes = szg_mip_chain_bytes(width, height);
+        if (chainBytes > 0 && hipMalloc(&mipChain, chainBytes) == hipSuccess)
+        {
+            szg_texture const level0 = texture();
+            if (szg_record_generate_mipmaps(nullptr, &level0, mipChain, chainBytes) == SZG_OK)
+            {
+                mipLevels = szg_mip_level_count(width, height);
+            }
+            else
+            {
+                (void)hipFree(mipChain);
+                mipChain = nullptr;
+            }
+        }
+        if (chainBytes > 0 && mipLevels <= 1)
+        {
+            std::fprintf(stderr, "[szg] Failed to build the mip chain of image '%s'; it keeps one level.\n", name.c_str());
+        }
+    }
+
+  public:
     void* data{nullptr};
     uint32_t width{0}, height{0};
     bool srgb{false};
@@ -199,7 +268,9 @@ class AssetLibrary
         return library;
     }
 
-    // assets.cpp:1192-1266; returns the number of meshes registered (the reference logs it)
+    // assets.cpp:1192-1266; returns the number of meshes registered (the reference logs it). `flags`: SZG_GLTF_* of szg/assets.h.
+    // With SZG_GLTF_DECODE_JPEG a JPEG map arrives like a PNG one; with SZG_GLTF_JPEG_FOR_DEVICE it is reconstructed on the GPU
+    // (ImageView::uploadJPEG) with the loader's channel overrides as masks.
     auto loadGLTFFromPath(std::filesystem::path const& filePath, uint32_t flags = 0) -> size_t
     {
         std::fprintf(stderr, "[szg] Loading glTF from %s\n", filePath.string().c_str());
@@ -220,9 +291,20 @@ class AssetLibrary
             szg_asset_material m{};
             (void)szg_gltf_material(asset, i, &m);
             MaterialData data{m_defaultORMMap, m_defaultNormalMap, m_defaultColorMap};
-            auto bring = [&](szg_asset_texture const& t, std::shared_ptr<ImageView const>& slot) {
+            auto bring = [&](szg_asset_texture const& t, int kind, std::shared_ptr<ImageView const>& slot) {
                 if (t.rgba == nullptr)
                 {
+                    szg_jpeg_map map{};
+                    if ((flags & SZG_GLTF_JPEG_FOR_DEVICE) != 0 && szg_gltf_material_jpeg(asset, i, kind, &map) == SZG_OK && map.jpeg != nullptr)
+                    {
+                        if (auto view = ImageView::uploadJPEG(map.jpeg, map.rgba_and, map.rgba_or, map.srgb != 0, deduplicateAssetName(map.name),
+                                                              m_generateMips);
+                            view != nullptr)
+                        {
+                            m_textures.push_back(view);
+                            slot = view;
+                        }
+                    }
                     return;
                 }
                 if (auto view = ImageView::upload(t.rgba, t.width, t.height, t.srgb != 0, deduplicateAssetName(t.name), m_generateMips);
@@ -232,9 +314,9 @@ class AssetLibrary
                     slot = view;
                 }
             };
-            bring(m.orm, data.ORM);
-            bring(m.color, data.color);
-            bring(m.normal, data.normal);
+            bring(m.orm, SZG_MAP_ORM, data.ORM);
+            bring(m.color, SZG_MAP_COLOR, data.color);
+            bring(m.normal, SZG_MAP_NORMAL, data.normal);
             materials.push_back(std::move(data));
         }
         size_t loaded = 0;
@@ -255,6 +337,29 @@ class AssetLibrary
     // assets.cpp:1131-1168 (fileFormat: sRGB or UNORM interpretation of the 8-bit texels)
     auto loadTextureFromPath(bool srgb, std::filesystem::path const& filePath) -> std::shared_ptr<ImageView const>
     {
+        if (m_decodeJPEG)
+        {
+            // szg/jpeg.h, opt-in: a file that is a JPEG stream is entropy-decoded here and reconstructed on the GPU
+            std::ifstream in(filePath, std::ios::binary);
+            std::vector<char> const bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            if (bytes.size() >= 2 && static_cast<uint8_t>(bytes[0]) == 0xFF && static_cast<uint8_t>(bytes[1]) == 0xD8)
+            {
+                szg_jpeg* jpeg = nullptr;
+                if (szg_jpeg_open(bytes.data(), bytes.size(), &jpeg) != SZG_OK)
+                {
+                    std::fprintf(stderr, "[szg] Failed to convert file to 32 bit RGBA image.\n");
+                    return nullptr;
+                }
+                auto view = ImageView::uploadJPEG(jpeg, 0xFFFFFFFFu, 0u, srgb, deduplicateAssetName("texture_" + filePath.stem().string()),
+                                                  m_generateMips);
+                szg_jpeg_destroy(jpeg);
+                if (view != nullptr)
+                {
+                    m_textures.push_back(view);
+                }
+                return view;
+            }
+        }
         uint32_t width = 0, height = 0;
         uint8_t* rgba = nullptr;
         if (int const status = szg_load_image_file_rgba(filePath.string().c_str(), &width, &height, &rgba); status != SZG_OK)
@@ -282,6 +387,9 @@ class AssetLibrary
     // default maps when loadDefaultAssets(true) set it) gets a full mip chain, owned by its ImageView. Off by default.
     void setGenerateMips(bool enable) { m_generateMips = enable; }
     [[nodiscard]] auto generateMips() const -> bool { return m_generateMips; }
+    // szg/jpeg.h: while the switch is on, loadTextureFromPath decodes JPEG files too (off by default: PNG only)
+    void setDecodeJPEG(bool enable) { m_decodeJPEG = enable; }
+    [[nodiscard]] auto decodeJPEG() const -> bool { return m_decodeJPEG; }
     // The table entries of every texture of this library that carries a chain, for DeferredShadingPipeline::setTextureMips.
     // Empty unless textures were loaded with the switch on.
     [[nodiscard]] auto textureMips() const -> std::vector<szg_texture_mips>
@@ -339,6 +447,7 @@ class AssetLibrary
     std::shared_ptr<ImageView const> m_defaultColorMap{}, m_defaultNormalMap{}, m_defaultORMMap{};
     std::vector<std::shared_ptr<ImageView const>> m_textures{};
     bool m_generateMips{false};
+    bool m_decodeJPEG{false};
     std::shared_ptr<Mesh const> m_meshPlane{}, m_meshCube{};
     std::vector<std::shared_ptr<Mesh const>> m_meshes{};
 };

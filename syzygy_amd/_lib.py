@@ -73,6 +73,12 @@ def lib():
             if "SZG_HIP_LIBRARY" not in os.environ:
                 raise RuntimeError(f"{path} predates include/szg/ui_layer.h ({e}); rebuild the library") from e
             print(f"[szg] {path} predates include/szg/ui_layer.h ({e}): the UI layer pass is unavailable with it", file=sys.stderr)
+        try:
+            abi.bind(handle, abi.JPEG_FUNCTIONS)
+        except AttributeError as e:
+            if "SZG_HIP_LIBRARY" not in os.environ:
+                raise RuntimeError(f"{path} predates include/szg/jpeg.h ({e}); rebuild the library") from e
+            print(f"[szg] {path} predates include/szg/jpeg.h ({e}): JPEG material maps are unavailable with it", file=sys.stderr)
         _LIB = handle
     return _LIB
 

@@ -649,6 +649,40 @@ UI_LAYER_FUNCTIONS = {
 }
 
 
+# include/szg/jpeg.h
+SZG_JPEG_MAX_EXTENT = 32768
+SZG_JPEG_GREY = 0
+SZG_JPEG_YCBCR = 1
+SZG_JPEG_RGB = 2
+SZG_GLTF_DECODE_JPEG = 2
+SZG_GLTF_JPEG_FOR_DEVICE = 4
+
+
+class JpegPlane(C.Structure):
+    _fields_ = [("coefficients", VP), ("h", U32), ("v", U32), ("width", U32), ("height", U32), ("blocks_w", U32),
+                ("blocks_h", U32)]
+
+
+class JpegFrame(C.Structure):
+    _fields_ = [("width", U32), ("height", U32), ("plane_count", U32), ("color", U32), ("h_max", U32), ("v_max", U32),
+                ("progressive", U32), ("planes", JpegPlane * 3)]
+
+
+class JpegMap(C.Structure):
+    _fields_ = [("jpeg", VP), ("rgba_and", U32), ("rgba_or", U32), ("srgb", U32), ("name", C.c_char_p)]
+
+
+JPEG_FUNCTIONS = {
+    "szg_jpeg_open": (C.c_int, [VP, C.c_size_t, P(VP)]),
+    "szg_jpeg_destroy": (None, [VP]),
+    "szg_jpeg_get_frame": (C.c_int, [VP, P(JpegFrame)]),
+    "szg_jpeg_reconstruct_host": (C.c_int, [P(JpegFrame), U32, U32, VP, C.c_size_t]),
+    "szg_jpeg_scratch_bytes": (C.c_size_t, [P(JpegFrame)]),
+    "szg_record_jpeg_reconstruct": (C.c_int, [VP, P(JpegFrame), VP, C.c_size_t, U32, U32, P(Image)]),
+    "szg_gltf_material_jpeg": (C.c_int, [VP, U32, C.c_int, P(JpegMap)]),
+}
+
+
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""
     for name, (restype, argtypes) in table.items():

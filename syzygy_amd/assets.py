@@ -43,6 +43,26 @@ def decode_image_rgba(data):
         lib().szg_free_rgba(ptr)
 
 
+def decode_jpeg_rgba(data, rgba_and=0xFFFFFFFF, rgba_or=0):
+    """JPEG bytes -> uint8 [h, w, 4] on the host (include/szg/jpeg.h: szg_jpeg_open + szg_jpeg_reconstruct_host); what the
+    reference's decoder answers a 4-channel request with. pipelines.decode_jpeg is the device path."""
+    data = bytes(data)
+    handle = C.c_void_p()
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    if lib().szg_jpeg_open(C.cast(buf, C.c_void_p), len(data), C.byref(handle)) != abi.SZG_OK:
+        raise AssetError(_last_error())
+    try:
+        frame = abi.JpegFrame()
+        lib().szg_jpeg_get_frame(handle, C.byref(frame))
+        out = np.empty((frame.height, frame.width, 4), np.uint8)
+        if lib().szg_jpeg_reconstruct_host(C.byref(frame), int(rgba_and), int(rgba_or), out.ctypes.data_as(C.c_void_p),
+                                           frame.width * 4) != abi.SZG_OK:
+            raise AssetError(_last_error())
+        return out
+    finally:
+        lib().szg_jpeg_destroy(handle)
+
+
 def load_image_rgba(path):
     """The file part of AssetLibrary::loadTextureFromPath (assets.cpp:1131-1168): an image file -> uint8 [h, w, 4]."""
     w, h, ptr = abi.U32(), abi.U32(), C.POINTER(C.c_uint8)()
@@ -121,7 +141,21 @@ def _texture(t):
     return (np.ctypeslib.as_array(t.rgba, shape=(t.height, t.width, 4)).copy(), bool(t.srgb)), t.name.decode(errors="replace")
 
 
-def _collect(handle):
+def _jpeg_texture(handle, material, kind, device):
+    """SZG_GLTF_JPEG_FOR_DEVICE: the map as a device tensor (reconstructed on the GPU, overrides applied there), or None when the
+    map is not a JPEG kept for the device."""
+    m = abi.JpegMap()
+    if lib().szg_gltf_material_jpeg(handle, material, kind, C.byref(m)) != abi.SZG_OK:
+        raise AssetError(_last_error())
+    if not m.jpeg:
+        return None
+    from . import pipelines
+
+    tensor = pipelines.reconstruct_jpeg(C.c_void_p(m.jpeg), m.rgba_and, m.rgba_or, device)
+    return (tensor, bool(m.srgb)), (m.name or b"").decode(errors="replace")
+
+
+def _collect(handle, flags=0, device="cuda"):
     L = lib()
     out_meshes, out_materials = [], []
     for i in range(L.szg_gltf_material_count(handle)):
@@ -129,8 +163,10 @@ def _collect(handle):
         if L.szg_gltf_material(handle, i, C.byref(m)) != abi.SZG_OK:
             raise AssetError(_last_error())
         record = {"name": (m.name or b"").decode(errors="replace"), "texture_names": {}}
-        for key in ("color", "normal", "orm"):
+        for key, kind in (("color", abi.SZG_MAP_COLOR), ("normal", abi.SZG_MAP_NORMAL), ("orm", abi.SZG_MAP_ORM)):
             tex = _texture(getattr(m, key))
+            if tex is None and flags & abi.SZG_GLTF_JPEG_FOR_DEVICE:
+                tex = _jpeg_texture(handle, i, kind, device)
             record[key] = tex[0] if tex else None
             record["texture_names"][key] = tex[1] if tex else ""
         out_materials.append(record)
@@ -143,19 +179,21 @@ def _collect(handle):
     return GltfAsset(out_meshes, out_materials, warnings)
 
 
-def load_gltf(path, flags=0):
-    """AssetLibrary::loadGLTFFromPath: '.gltf' is read as JSON, anything else as GLB (assets.cpp:422-430)."""
+def load_gltf(path, flags=0, device="cuda"):
+    """AssetLibrary::loadGLTFFromPath: '.gltf' is read as JSON, anything else as GLB (assets.cpp:422-430). `flags`: abi.SZG_GLTF_*;
+    with SZG_GLTF_JPEG_FOR_DEVICE a material map that is a JPEG stream is a uint8 tensor on `device` (reconstructed there by
+    pipelines.reconstruct_jpeg) where the other maps are numpy arrays; meshes.MeshInstanced takes both."""
     handle = C.c_void_p()
     status = lib().szg_gltf_load_file(os.fsencode(path), int(flags), C.byref(handle))
     if status != abi.SZG_OK:
         raise AssetError(f"{_last_error()} (status {status})")
     try:
-        return _collect(handle)
+        return _collect(handle, int(flags), device)
     finally:
         lib().szg_gltf_destroy(handle)
 
 
-def load_gltf_bytes(data, is_glb, asset_root=None, flags=0):
+def load_gltf_bytes(data, is_glb, asset_root=None, flags=0, device="cuda"):
     data = bytes(data)
     handle = C.c_void_p()
     buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
@@ -164,6 +202,6 @@ def load_gltf_bytes(data, is_glb, asset_root=None, flags=0):
     if status != abi.SZG_OK:
         raise AssetError(f"{_last_error()} (status {status})")
     try:
-        return _collect(handle)
+        return _collect(handle, int(flags), device)
     finally:
         lib().szg_gltf_destroy(handle)

@@ -1,7 +1,8 @@
 // host_assets.cpp — szg/assets.h: glTF 2.0 / GLB -> meshes, surfaces and material maps for the raster passes
 // (assets/assets.cpp:406-1092, :1192-1266). CPU only, no third-party code: a small JSON reader, base64, inflate and a
 // PNG decoder stand where the reference calls fastgltf (a FetchContent download, not in the checkout) and stb_image
-// (vendored under thirdparty/stb; not used or restated here — PNG is decoded from its specification, JPEG is refused).
+// (vendored under thirdparty/stb; not used or restated here — PNG is decoded from its specification, JPEG is refused unless
+// a flag of szg/jpeg.h asks for it: then host_jpeg.cpp decodes it).
 // Out of the hot path's scope and frozen: it only feeds the rasteriser's tests.
 #include <algorithm>
 #include <cmath>
@@ -21,7 +22,20 @@
 #include <vector>
 
 #include "szg/assets.h"
+#include "szg/jpeg.h"
 #include "szg_internal.hpp"
+
+// host_jpeg.cpp and api_core.cpp define these. They are WEAK references here because this file is also built without them
+// into CPU-only test programs (tests/cpp/fuzz_assets): there the flags of szg/jpeg.h find no decoder, and a JPEG image fails
+// like any undecodable image. In libszg_hip.so they always resolve.
+extern "C" {
+__attribute__((weak)) int szg_jpeg_open(const void* bytes, size_t size, szg_jpeg** out);
+__attribute__((weak)) void szg_jpeg_destroy(szg_jpeg* jpeg);
+__attribute__((weak)) int szg_jpeg_get_frame(const szg_jpeg* jpeg, szg_jpeg_frame* out);
+__attribute__((weak)) int szg_jpeg_reconstruct_host(const szg_jpeg_frame* frame, uint32_t rgba_and, uint32_t rgba_or, uint8_t* rgba,
+                                                    size_t pitch_bytes);
+__attribute__((weak)) const char* szg_last_error(void);
+}
 
 namespace
 {
@@ -1250,6 +1264,10 @@ struct TextureData
     uint32_t srgb = 0;
     std::string name;
     bool present = false;
+    // SZG_GLTF_JPEG_FOR_DEVICE (szg/jpeg.h): the entropy-decoded stream instead of rgba (owned by the asset), and the
+    // channel overrides as the masks of rule 5
+    const szg_jpeg* jpeg = nullptr;
+    uint32_t rgbaAnd = 0xFFFFFFFFu, rgbaOr = 0u;
 };
 struct MaterialRecord
 {
@@ -1343,6 +1361,17 @@ struct szg_gltf
     std::vector<MeshRecord> meshes;
     std::vector<MaterialRecord> materials;
     std::string warnings;
+    std::vector<szg_jpeg*> jpegs; // SZG_GLTF_JPEG_FOR_DEVICE: one per JPEG image kept for the device
+    szg_gltf() = default;
+    szg_gltf(const szg_gltf&) = delete;
+    szg_gltf& operator=(const szg_gltf&) = delete;
+    ~szg_gltf()
+    {
+        for (szg_jpeg* j : jpegs)
+        {
+            szg_jpeg_destroy(j);
+        }
+    }
 };
 
 namespace
@@ -1434,6 +1463,7 @@ class Loader
         bool tried = false, ok = false;
         uint32_t width = 0, height = 0;
         Bytes rgba;
+        const szg_jpeg* jpeg = nullptr; // SZG_GLTF_JPEG_FOR_DEVICE: rgba stays empty
     };
     std::vector<DecodedImage> images_;
     int jpegRefused_ = 0; // images refused because they are JPEG streams (decodeImageBytes), for the summary warning
@@ -1683,14 +1713,64 @@ class Loader
             return false;
         }
         std::string why;
+        bool const isJpeg = bytes.size() >= 2 && bytes[0] == 0xFF && bytes[1] == 0xD8;
+        if (isJpeg && (flags_ & (SZG_GLTF_DECODE_JPEG | SZG_GLTF_JPEG_FOR_DEVICE)) != 0)
+        {
+            // szg/jpeg.h: opt-in; the stream is treated like a decoded PNG from here on
+            if (!decodeJpeg(bytes, d, why))
+            {
+                warn("stbi: Failed to convert image. (" + what + ": " + why + ")");
+                warn("Failed to load image from glTF.");
+                return false;
+            }
+            d.ok = true;
+            return true;
+        }
         if (!decodeImageBytes(bytes.data(), bytes.size(), d.width, d.height, d.rgba, why))
         {
             warn("stbi: Failed to convert image. (" + what + ": " + why + ")");
             warn("Failed to load image from glTF.");
-            jpegRefused_ += (bytes.size() >= 2 && bytes[0] == 0xFF && bytes[1] == 0xD8) ? 1 : 0;
+            jpegRefused_ += isJpeg ? 1 : 0;
             return false;
         }
         d.ok = true;
+        return true;
+    }
+
+    // SZG_GLTF_DECODE_JPEG: entropy decode + host reconstruction; SZG_GLTF_JPEG_FOR_DEVICE: the entropy decode alone
+    bool decodeJpeg(Bytes const& bytes, DecodedImage& d, std::string& why)
+    {
+        szg_jpeg* jpeg = nullptr;
+        if (&szg_jpeg_open == nullptr || &szg_jpeg_destroy == nullptr || &szg_jpeg_get_frame == nullptr ||
+            &szg_jpeg_reconstruct_host == nullptr || &szg_last_error == nullptr)
+        {
+            why = "no JPEG decoder is linked into this build";
+            return false;
+        }
+        if (szg_jpeg_open(bytes.data(), bytes.size(), &jpeg) != SZG_OK)
+        {
+            why = szg_last_error();
+            return false;
+        }
+        szg_jpeg_frame frame;
+        szg_jpeg_get_frame(jpeg, &frame);
+        d.width = frame.width;
+        d.height = frame.height;
+        if ((flags_ & SZG_GLTF_JPEG_FOR_DEVICE) != 0)
+        {
+            out_.jpegs.push_back(jpeg);
+            d.jpeg = jpeg;
+            return true;
+        }
+        d.rgba.resize(size_t{frame.width} * frame.height * 4u);
+        int const status = szg_jpeg_reconstruct_host(&frame, 0xFFFFFFFFu, 0u, d.rgba.data(), size_t{frame.width} * 4u);
+        szg_jpeg_destroy(jpeg);
+        if (status != SZG_OK)
+        {
+            why = szg_last_error();
+            d.rgba.clear();
+            return false;
+        }
         return true;
     }
 
@@ -1735,6 +1815,20 @@ class Loader
         out.width = d.width;
         out.height = d.height;
         out.srgb = srgb ? 1u : 0u;
+        out.jpeg = d.jpeg;
+        if (d.jpeg != nullptr)
+        {
+            // the same overrides as masks on the texel dword (R lowest), applied by the device reconstruction
+            const std::optional<uint8_t>* const channel[4] = {&overrides.red, &overrides.green, &overrides.blue, &overrides.alpha};
+            for (unsigned c = 0; c < 4u; c++)
+            {
+                if (channel[c]->has_value())
+                {
+                    out.rgbaAnd &= ~(0xFFu << (8u * c));
+                    out.rgbaOr |= uint32_t{channel[c]->value()} << (8u * c);
+                }
+            }
+        }
         // channel overrides, assets.cpp:551-573
         for (size_t i = 0; i + 3 < out.rgba.size(); i += 4)
         {
@@ -2039,7 +2133,7 @@ int finish(int status, const std::string& error, std::unique_ptr<szg_gltf>& asse
 
 void fillTexture(const TextureData& t, szg_asset_texture* out)
 {
-    out->rgba = t.present ? t.rgba.data() : nullptr;
+    out->rgba = t.present && t.jpeg == nullptr ? t.rgba.data() : nullptr; // a JPEG kept for the device has no host texels
     out->width = t.present ? t.width : 0;
     out->height = t.present ? t.height : 0;
     out->srgb = t.srgb;
@@ -2137,6 +2231,23 @@ int szg_gltf_material(const szg_gltf* asset, uint32_t index, szg_asset_material*
     fillTexture(m.color, &out->color);
     fillTexture(m.normal, &out->normal);
     fillTexture(m.orm, &out->orm);
+    return SZG_OK;
+}
+
+int szg_gltf_material_jpeg(const szg_gltf* asset, uint32_t material, int kind, szg_jpeg_map* out)
+{
+    if (asset == nullptr || out == nullptr || material >= asset->materials.size() || kind < SZG_MAP_COLOR || kind > SZG_MAP_ORM)
+    {
+        szg::set_last_error("szg_gltf_material_jpeg: NULL argument, index out of range or unknown kind");
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
+    MaterialRecord const& m = asset->materials[material];
+    TextureData const& t = kind == SZG_MAP_COLOR ? m.color : (kind == SZG_MAP_NORMAL ? m.normal : m.orm);
+    out->jpeg = t.present ? t.jpeg : nullptr;
+    out->rgba_and = t.rgbaAnd;
+    out->rgba_or = t.rgbaOr;
+    out->srgb = t.srgb;
+    out->name = t.name.c_str();
     return SZG_OK;
 }
 

@@ -96,7 +96,8 @@ def inverse_transpose(m):
 
 class MeshInstanced:
     """One mesh with its surfaces and instance transforms. `surfaces` = [(first_index, index_count, material)], a
-    material being {"color"|"normal"|"orm": (uint8 [h, w, 4] array, srgb flag)}. `mipmaps=True` builds a full mip chain for
+    material being {"color"|"normal"|"orm": (uint8 [h, w, 4] array, srgb flag)}; a map may also be a contiguous uint8 [h, w, 4]
+    tensor that already lives on the GPU (pipelines.decode_jpeg), which is sampled as is. `mipmaps=True` builds a full mip chain for
     every texture on upload (include/szg/mipmaps.h); register them with register_texture_mips()."""
 
     def __init__(self, vertices, indices, surfaces, models, render=True, casts_shadow=True, name="", mipmaps=False):
@@ -129,11 +130,20 @@ class MeshInstanced:
         for _, _, material in self.surfaces:
             for key, (tex, _) in material.items():
                 if id(tex) not in d["textures"]:
-                    d["textures"][id(tex)] = up(tex)
+                    # a map that already is a device tensor (a JPEG reconstructed on the GPU, pipelines.decode_jpeg) is used as is
+                    d["textures"][id(tex)] = self._device_map(tex) if isinstance(tex, torch.Tensor) else up(tex)
         d["mips"] = {}
         self._device = d
         self._ensure_mips(d)
         return d
+
+    @staticmethod
+    def _device_map(tex):
+        import torch
+
+        if not tex.is_cuda or tex.dtype != torch.uint8 or tex.dim() != 3 or tex.shape[2] != 4 or not tex.is_contiguous():
+            raise ValueError("a material map given as a tensor must be a contiguous uint8 [h, w, 4] tensor on the GPU")
+        return tex
 
     def _ensure_mips(self, d):
         """Chains for every texture while `mipmaps` is set, whenever it was set: built once, dropped when it is cleared."""
@@ -185,6 +195,10 @@ class MeshInstanced:
 
     def host_struct(self):
         host = {"vertices": self.vertices, "indices": self.indices, "models": self._models_np, "mits": self._mits_np}
+        for _, _, material in self.surfaces:
+            for tex, _ in material.values():
+                if not isinstance(tex, np.ndarray):
+                    raise TypeError("host_struct: a material map of this mesh lives on the device; the host oracle needs numpy maps")
         return self._struct(lambda k: host[k].ctypes.data, lambda tex: tex.ctypes.data)
 
 

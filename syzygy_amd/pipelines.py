@@ -217,6 +217,67 @@ def generate_mipmaps(texture, srgb, cmd=None):
 
 
 # ---------------------------------------------------------------------------
+# JPEG material maps (include/szg/jpeg.h)
+# ---------------------------------------------------------------------------
+def upload_jpeg_frame(frame, device="cuda"):
+    """Copy the coefficient planes of a HOST frame (szg_jpeg_get_frame) to `device`: (abi.JpegFrame with DEVICE pointers, the
+    tensors that own them). The copies are complete when this returns, so the szg_jpeg may be destroyed."""
+    out = abi.JpegFrame.from_buffer_copy(frame)
+    keep = []
+    for k in range(frame.plane_count):
+        p = frame.planes[k]
+        n = p.blocks_w * p.blocks_h * 64
+        host = np.ctypeslib.as_array(C.cast(p.coefficients, C.POINTER(C.c_int16)), shape=(n,))
+        keep.append(torch.from_numpy(host.copy()).to(device))
+        out.planes[k].coefficients = keep[-1].data_ptr()
+    return out, keep
+
+
+def record_jpeg_reconstruct(frame, dst, rgba_and=0xFFFFFFFF, rgba_or=0, cmd=None, scratch=None):
+    """szg_record_jpeg_reconstruct of a frame with DEVICE pointers into `dst`, a uint8 CUDA tensor [h, w, 4] whose rows may be
+    strided and which may be larger than the frame. Returns the scratch tensor (keep it until the stream has run)."""
+    if dst.dtype != torch.uint8 or dst.dim() != 3 or dst.shape[2] != 4 or dst.stride(2) != 1 or dst.stride(1) != 4:
+        raise ValueError("record_jpeg_reconstruct: expected a uint8 tensor [h, w, 4] with contiguous texels")
+    h, w = int(dst.shape[0]), int(dst.shape[1])
+    nbytes = lib().szg_jpeg_scratch_bytes(C.byref(frame))
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dst.device)
+    im = abi.Image()
+    im.data, im.width, im.height, im.format = dst.data_ptr(), w, h, abi.SZG_FORMAT_RGBA8_UNORM
+    im.pitch_bytes = int(dst.stride(0)) if h > 1 else w * 4
+    check(lib().szg_record_jpeg_reconstruct(_stream_handle(cmd), C.byref(frame), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                            int(rgba_and), int(rgba_or), C.byref(im)))
+    return scratch
+
+
+def reconstruct_jpeg(handle, rgba_and=0xFFFFFFFF, rgba_or=0, device="cuda", cmd=None):
+    """An open szg_jpeg -> uint8 [h, w, 4] tensor on `device`: coefficient upload, then k_jpeg_idct and k_jpeg_color on `cmd` (the
+    current stream by default). The handle is not needed once this returns."""
+    frame = abi.JpegFrame()
+    check(lib().szg_jpeg_get_frame(handle, C.byref(frame)))
+    stream = torch.cuda.current_stream(device) if cmd is None else cmd
+    with torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _NullCtx():
+        d_frame, keep = upload_jpeg_frame(frame, device)
+        out = torch.empty((frame.height, frame.width, 4), dtype=torch.uint8, device=device)
+        keep.append(record_jpeg_reconstruct(d_frame, out, rgba_and, rgba_or, stream))
+    # coefficients and scratch go back to torch's allocator here: it hands them out again in stream order, behind the kernels
+    return out
+
+
+def decode_jpeg(data, rgba_and=0xFFFFFFFF, rgba_or=0, device="cuda", cmd=None):
+    """JPEG bytes -> uint8 [h, w, 4] tensor on `device`: szg_jpeg_open on the host (entropy decode), the reconstruction on the
+    GPU. (texel & rgba_and) | rgba_or is applied to every texel as a little-endian dword, R lowest (jpeg.h rule 5)."""
+    data = bytes(data)
+    handle = C.c_void_p()
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    check(lib().szg_jpeg_open(C.cast(buf, C.c_void_p), len(data), C.byref(handle)))
+    try:
+        return reconstruct_jpeg(handle, rgba_and, rgba_or, device, cmd)
+    finally:
+        lib().szg_jpeg_destroy(handle)
+
+
+# ---------------------------------------------------------------------------
 # Present pass (include/szg/present.h)
 # ---------------------------------------------------------------------------
 def _as_rect(r):
