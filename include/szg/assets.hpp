@@ -49,7 +49,9 @@ inline auto uploadBytes(void const* host, size_t bytes) -> void*
     {
         return nullptr;
     }
-    if (hipMemcpy(device, host, bytes, hipMemcpyHostToDevice) != hipSuccess)
+    // (from pageable memory the copy may return once the source is staged; passes recorded on a non-blocking stream do not wait
+    // for the null stream it runs on)
+    if (hipMemcpy(device, host, bytes, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
     {
         (void)hipFree(device);
         return nullptr;

@@ -223,8 +223,10 @@ struct SceneTexture
         auto t = std::make_unique<SceneTexture>();
         auto image = [&](szg_image& im, uint32_t fmt, uint32_t texel) {
             im = szg_image{nullptr, width, height, width * texel, fmt};
+            // (the fill runs on the null stream and is not promised to be complete on return; the first pass may be recorded on
+            // a non-blocking stream, which does not wait for the null stream: wait here, once)
             return hipMalloc(&im.data, (size_t)width * height * texel) == hipSuccess &&
-                   hipMemset(im.data, 0, (size_t)width * height * texel) == hipSuccess;
+                   hipMemset(im.data, 0, (size_t)width * height * texel) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
         };
         bool ok = image(t->m_texture.color, SZG_FORMAT_RGBA16_UNORM, 8) && image(t->m_texture.depth, SZG_FORMAT_D32_SFLOAT, 4);
         if (ok && debugColor)

@@ -112,7 +112,17 @@ typedef struct szg_mesh_instanced
     uint32_t casts_shadow;                       /* MeshInstanced::castsShadow */
 } szg_mesh_instanced;
 
-/* The G-buffer pass of DeferredShadingPipeline::recordDrawCommands (deferred.cpp:493-713): clears the five
+/* HOST WAITS of the three calls below. They are enqueued on `stream` and return without waiting for the device, with two
+ * exceptions, both by design:
+ *   - growth: the pipeline keeps its draw records and per-primitive buffers and grows them on demand. A call that needs more
+ *     draws or primitives than any call before it on this pipeline waits for `stream` (hipStreamSynchronize: earlier frames
+ *     in flight on it still read the old buffers), frees them and allocates larger ones. Frames recorded before and after are
+ *     unaffected; a caller that must never wait records its largest scene once up front;
+ *   - staging-ring wrap: spot lights, shadow slots and draw records go through a ring of 8 pinned buffers (5 uploads per
+ *     szg_deferred_record_draw_commands_meshes with spot lights and owned maps). An upload whose slot is still waiting for
+ *     its copy of an earlier frame to run waits for that copy.
+ *
+ * The G-buffer pass of DeferredShadingPipeline::recordDrawCommands (deferred.cpp:493-713): clears the five
  * G-buffer planes and scene_texture->depth over the draw rect and rasterises every rendered mesh into them.
  * Row tiles as in abi.h (a rank rasterises only its rows). The whole scene texture is checked, as by
  * szg_deferred_record_gbuffer_fill: a missing or malformed colour image (or debug_color, when present) is refused although

@@ -113,7 +113,10 @@ template <typename T> class DeviceBuffer
             ptr = nullptr;
         }
     }
-    // `count` elements (bytes of a DeviceBuffer<void>), optionally zero-filled; what was held before is freed first
+    // `count` elements (bytes of a DeviceBuffer<void>), optionally zero-filled; what was held before is freed first.
+    // The zeros are there when alloc returns: hipMemset runs on the null stream, and neither its documentation nor
+    // hipMemsetAsync's promises that a fill of device memory has completed when the call returns. A record call on a
+    // non-blocking stream does not wait for the null stream, so alloc does (create time only).
     hipError_t alloc(size_t count, bool zero = false)
     {
         reset();
@@ -122,6 +125,10 @@ template <typename T> class DeviceBuffer
         if (e == hipSuccess && zero)
         {
             e = hipMemset(ptr, 0, bytes);
+            if (e == hipSuccess)
+            {
+                e = hipStreamSynchronize(nullptr);
+            }
         }
         return e;
     }

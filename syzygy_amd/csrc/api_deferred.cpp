@@ -69,6 +69,9 @@ int szg_deferred_create(szg_deferred_t** out, const szg_deferred_desc* desc, int
                                   desc->shadow_map_dim, desc->shadow_map_dim, 0u};
         }
         SZG_TRY(hipMemcpy(p->d_ownedSlots, owned.data(), owned.size() * sizeof(ShadowSlot), hipMemcpyHostToDevice));
+        // from pageable memory the call may return when the source has been staged, before the device holds it; the
+        // first record call may come on a non-blocking stream, which does not wait for the null stream
+        SZG_TRY(hipStreamSynchronize(nullptr));
     }
 #undef SZG_TRY
     size_t stagingBytes = (size_t)nSpots * sizeof(szg_spot_light_packed);
