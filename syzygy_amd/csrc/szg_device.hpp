@@ -221,7 +221,9 @@ SZG_DEV bool slutTexelFinite(float r, float g, float b) { return fabsf(r) <= 0x1
 SZG_DEV bool inRange(float x, float lo, float hi) { return x >= lo && x <= hi; } // false for NaN
 SZG_DEV float divN0(float a, float b) { return divR0(a, b, rcpN(b)); }
 // true when `c` holds on every active lane: one compare into a lane mask and one scalar test (HIP's __all() builds two
-// ballots from an int predicate, ~15 instructions per use)
+// ballots from an int predicate, ~15 instructions per use). Lanes switched off by divergence - a call under a divergent `if`,
+// lanes that have left the kernel - do not take part: the ballot has 0 for them, so their values can neither open nor close a
+// gate (tests/test_gpu_march_rays.py runs the march with every third lane, and with all lanes but one, switched off).
 SZG_DEV bool waveAll(bool c) { return __builtin_amdgcn_ballot_w64(!c) == 0ull; }
 
 // szg_powf(x, y) (szg/fpmath.h: exp(y * log x) with GLSL's special cases) for a base that is a positive NORMAL number

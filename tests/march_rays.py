@@ -1,0 +1,587 @@
+"""Rays for scatteringIntegral / marchLoop (syzygy_amd/csrc/szg_device.hpp), one at a time, and the waves to put them in.
+
+The march chooses among its arithmetic forms PER WAVE: a gate holds when its predicate holds on every active lane. This
+module builds, with numpy only,
+
+* FAMILIES of rays: each a sweep of one knob across one gate's threshold - a dense core of steps of one float32 ulp of the
+  gate quantity, at least 64 on each side of the crossing predicted in float64, and sparse points at relative distances
+  2^-16, 2^-12, 2^-9 and 2^-6 - every other per-ray gate held away from its own threshold; a few families of points or
+  ranges for the gates taken again at every step; and seeded random rays;
+* one SPOILER per set-up gate: a ray far on the failing side of that gate;
+* the WAVE FORMS of a family (layout()): uniform, natural, spoiled, holes, single active lanes;
+* a CENSUS: the per-ray predicates of scatteringIntegral restated in float64 from its text, each `true`, `false` or `near`
+  (within 2^-10 relative of the threshold). It is asked only about rays that are meant to lie far from a threshold: where
+  float32 puts the threshold inside a sweep is nobody's business, every lane is compared with the scalar oracle.
+
+tests/test_march_rays.py checks the construction without a GPU; tests/test_gpu_march_rays.py runs the forms.
+"""
+import copy
+import ctypes as C
+import math
+
+import numpy as np
+
+NEAR = 2.0 ** -10
+SETUP_GATES = ("setupLean", "lean", "extLean", "firstStepOnly", "belowOzone", "inner", "sunClear")
+# sub-predicates and nominal per-step quantities the census also states (swept by some families, never spoiled)
+AUX_GATES = ("sunPositive", "segmentNominal", "sunAboveHorizon")
+OUTER = (2.0 ** -16, 2.0 ** -12, 2.0 ** -9, 2.0 ** -6)
+CORE = 100  # steps of one ulp of the gate quantity on each side of the predicted crossing (>= 64 wanted)
+SPOILER_LANES = (0, 27, 63)
+SENTINEL = 0xDEADBEEF
+HOLE = 1
+BASE_EXTENT = (128, 32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The atmosphere block in float64 (load_atm's text) and a ray from its march parameters
+# ---------------------------------------------------------------------------------------------------------------------------
+class Bounds:
+    """The constants load_atm() derives from a packed block, in float64."""
+
+    def __init__(self, atm):
+        self.Rp, self.Ra = float(atm.planetRadiusMm), float(atm.atmosphereRadiusMm)
+        self.HR, self.HM = float(atm.densityScaleRayleighMm), float(atm.densityScaleMieMm)
+        self.sun = np.array(list(atm.incidentDirectionSun), np.float64)
+        self.sun2 = float(self.sun @ self.sun)
+        self.sinR, self.cosR = math.sin(float(atm.sunAngularRadius)), math.cos(float(atm.sunAngularRadius))
+        hmin = min(self.HR, self.HM)
+        self.leanFloor = max(0.9 * self.Rp, self.Rp - 80.0 * hmin)
+        self.extFloor = max(0.9 * self.Rp, self.Rp - 27.0 * hmin)
+        self.extCeil = self.Ra + (self.Ra - self.Rp) * 0.005
+        self.innerCeil = min(self.Ra * (1.0 - 2.0 ** -10), self.Rp + 85.0 * hmin)
+        self.ozoneLow = self.Rp + float(np.float32(0.0099))
+        # a frame around the direction TO the sun: s, and p, q perpendicular to it
+        self.s = -self.sun / math.sqrt(self.sun2)
+        k = np.array([1.0, 0.0, 0.0]) if abs(self.s[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+        self.p = np.cross(self.s, k)
+        self.p /= np.linalg.norm(self.p)
+        self.q = np.cross(self.s, self.p)
+
+
+def ray64(B, r, mu, D, sun_cos, scale=1.0, az=0.7):
+    """The ray (float64, 7 values) whose origin has radius r and sun cosine sun_cos, whose direction makes the cosine mu with the
+    local vertical at azimuth az from the great circle away from the sun, scaled by `scale`, with sample distance D."""
+    sn = math.sqrt(max(0.0, 1.0 - sun_cos * sun_cos))
+    up = sun_cos * B.s + sn * B.p
+    t1 = -sn * B.s + sun_cos * B.p
+    w = math.cos(az) * t1 + math.sin(az) * B.q
+    d = mu * up + math.sqrt(max(0.0, 1.0 - mu * mu)) * w
+    return np.concatenate([r * up, scale * d, [D]])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Census
+# ---------------------------------------------------------------------------------------------------------------------------
+def _cmp(q, thr, sense, scale=None):
+    """q >= thr (sense +1) or q <= thr (sense -1): 1 true, -1 false, 0 within NEAR of the threshold. NaN: false."""
+    if math.isnan(q):
+        return -1
+    if math.isinf(q):
+        return 1 if (q > thr) == (sense > 0) else -1
+    s = abs(thr) if scale is None else scale
+    if abs(q - thr) <= NEAR * s:
+        return 0
+    return 1 if (q - thr) * sense > 0 else -1
+
+
+def _all(*c):
+    return "false" if -1 in c else "near" if 0 in c else "true"
+
+
+def census(ray, B, atm_lean=True, ext_moderate=True):
+    """gate -> 'true' | 'false' | 'near' for one ray (7 numbers), from the text of scatteringIntegral (the per-ray predicates of
+    setupLean, lean, extLean, firstStepOnly, belowOzone, sunClear and the INNER choice), in float64. The four gates the kernel
+    conjoins with `lean` are stated WITHOUT it: their own term. Also the quantities, under 'q'."""
+    ray = np.asarray(ray, np.float64)
+    o, d, D = ray[0:3], ray[3:6], float(ray[6])
+    with np.errstate(all="ignore"):
+        origin2, direction2 = float(o @ o), float(d @ d)
+        radius, lenD = math.sqrt(origin2), math.sqrt(direction2)
+        mu = float(np.float64(o @ d) / np.float64(radius * lenD))
+        mu_sun = float(np.float64(o @ -B.sun) / np.float64(radius * math.sqrt(B.sun2)))
+        r_mu, r2 = radius * mu, radius * radius
+        L2 = float(np.float64(2.0 * radius * mu) * D + np.float64(D) * D + r2)
+        tStar = -r_mu
+        rmin2 = r2 * (1.0 - mu * mu) if (tStar > 0.0 and tStar < D) else float(np.fmin(r2, L2))
+        dS = D / 32.0
+        maxr2 = float(np.fmax(r2, L2))
+        rMax = math.sqrt(maxr2) if maxr2 >= 0 and not math.isinf(maxr2) else float(np.sqrt(np.float64(maxr2)))
+        r_musun = radius * mu_sun
+        hz = -math.sqrt(max(0.0, 1.0 - (B.Rp / radius) ** 2)) if radius > 0 else float("nan")
+    lo60, hi60, lo30, hi30 = 2.0 ** -60, 2.0 ** 60, 2.0 ** -30, 2.0 ** 30
+    flag = lambda b: 1 if b else -1
+    length2 = lambda x: (_cmp(x, lo60, 1), _cmp(x, hi60, -1))
+    out = {}
+    out["setupLean"] = _all(flag(atm_lean), _cmp(origin2, B.leanFloor ** 2, 1), _cmp(origin2, hi60, -1), *length2(direction2),
+                            *length2(B.sun2))
+    out["lean"] = _all(flag(atm_lean), _cmp(rmin2, B.leanFloor ** 2, 1), _cmp(radius, lo30, 1), _cmp(radius, hi30, -1),
+                       flag(D >= 0.0), _cmp(D, hi30, -1), _cmp(B.sinR, lo30, 1), *length2(B.sun2), *length2(direction2),
+                       _cmp(abs(mu), 2.0, -1), _cmp(abs(mu_sun), 2.0, -1))
+    out["extLean"] = _all(flag(ext_moderate), _cmp(rmin2, B.extFloor ** 2, 1), _cmp(maxr2, B.extCeil ** 2, -1))
+    out["firstStepOnly"] = _all(_cmp(dS, float(np.float32(0.0000001)), 1))
+    out["belowOzone"] = _all(_cmp(maxr2, B.ozoneLow ** 2, -1))
+    out["inner"] = _all(_cmp(maxr2, B.innerCeil ** 2, -1))
+    out["sunPositive"] = _all(_cmp(r_musun, 0.0, 1, scale=radius))
+    clearThreshold = (1.25 * B.sinR + 2.0 ** -10) * rMax / 0.999
+    out["sunClear"] = _all(flag(B.cosR >= 0.0), flag(B.sinR > 0.0), _cmp(r_musun, 0.0, 1, scale=radius),
+                           _cmp(r_musun, clearThreshold, 1))
+    # nominal per-step quantities: the squared step of a unit direction, and the sun against the origin's geometric horizon
+    out["segmentNominal"] = _all(_cmp(dS * dS, 2.0 ** -90, 1))
+    out["sunAboveHorizon"] = _all(_cmp(mu_sun, hz, 1, scale=1.0))
+    out["q"] = dict(origin2=origin2, direction2=direction2, radius=radius, mu=mu, mu_sun=mu_sun, rmin2=rmin2, maxr2=maxr2, dS=dS,
+                    D=D, r_musun=r_musun, clearThreshold=clearThreshold, horizon=hz)
+    return out
+
+
+def census_line(c):
+    q = c["q"]
+    gates = " ".join("%s=%s" % (g, c[g]) for g in SETUP_GATES + AUX_GATES)
+    return gates + " | " + " ".join("%s=%.9g" % (k, v) for k, v in q.items())
+
+
+def sun_step_states(ray, B):
+    """Per step i = 0 .. 31: does the sun disc clear the sample's horizon (ssNum >= ssDen of marchLoop), in float64."""
+    c = census(ray, B)["q"]
+    r, mu, mu_sun, dS = c["radius"], c["mu"], c["mu_sun"], c["dS"]
+    both = math.sqrt(max(0.0, mu_sun * mu - math.sqrt(max(0.0, (1 - mu_sun ** 2) * (1 - mu ** 2)))))
+    out = []
+    for i in range(32):
+        t = i * dS
+        sr = math.sqrt(max(0.0, 2 * r * mu * t + t * t + r * r))
+        s_musun = (t * both + r * mu_sun) / sr
+        sin_hz = B.Rp / sr
+        cos_hz = -math.sqrt(max(0.0, 1 - sin_hz ** 2))
+        out.append(s_musun - cos_hz * B.cosR + sin_hz * B.sinR >= 2 * sin_hz * B.sinR)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Families
+# ---------------------------------------------------------------------------------------------------------------------------
+class Family:
+    def __init__(self, name, gate, kind, knobs, rays, spoiler, coupled=()):
+        self.name, self.gate, self.kind, self.spoiler, self.coupled = name, gate, kind, spoiler, frozenset(coupled)
+        rays = np.asarray(rays, np.float64).astype(np.float32)
+        # identical float32 rays of neighbouring knob values are one ray
+        keep = [0] + [i for i in range(1, len(rays)) if rays[i].tobytes() != rays[i - 1].tobytes()]
+        self.rays = np.ascontiguousarray(rays[keep])
+        self.knobs = [knobs[i] for i in keep]
+
+    def __len__(self):
+        return len(self.rays)
+
+
+def _sweep(B, name, gate, make, quantity, thr, lo, hi, spoiler, coupled=(), scale=None):
+    """The family of make(x) for x around the root x0 of quantity(x) = thr in [lo, hi] (float64 bisection): x0 + k dx,
+    |k| <= CORE, dx moving the gate quantity by one float32 ulp of the threshold (of `scale` where the threshold is 0), and
+    x0 +- delta S / |dq/dx| for the OUTER deltas, clipped to [lo, hi]."""
+    f = lambda x: census(make(x), B)["q"][quantity] if isinstance(quantity, str) else quantity(make(x))
+    g = lambda x: f(x) - thr
+    a, b = lo, hi
+    ga, gb = g(a), g(b)
+    assert ga * gb < 0, (name, a, ga, b, gb)
+    for _ in range(200):
+        m = 0.5 * (a + b)
+        gm = g(m)
+        if (gm < 0) == (ga < 0):
+            a, ga = m, gm
+        else:
+            b = m
+    x0 = 0.5 * (a + b)
+    h = 1e-4 * (hi - lo)
+    dq = abs(f(min(x0 + h, hi)) - f(max(x0 - h, lo))) / (min(x0 + h, hi) - max(x0 - h, lo))
+    S = abs(thr) if scale is None else scale
+    ulp = 2.0 ** (math.floor(math.log2(S)) - 23)
+    dx = ulp / dq
+    xs = [x0 + k * dx for k in range(-CORE, CORE + 1)]
+    for delta in OUTER:
+        xs += [x0 - delta * S / dq, x0 + delta * S / dq]
+    xs = sorted(set(min(max(x, lo), hi) for x in xs))
+    return Family(name, gate, "sweep", xs, [make(x) for x in xs], spoiler, coupled)
+
+
+SUN_HIGH = 0.9  # sun cosine at the origin of the rays that are to be sunClear
+
+
+def spoilers(B):
+    """gate -> the ray (float32) far on the failing side of that set-up gate."""
+    low = B.Rp + 0.001
+    mid = math.sqrt(0.5 * (B.innerCeil ** 2 + B.extCeil ** 2))  # between the INNER and the extinction ceilings
+    s = {
+        "setupLean": ray64(B, B.Rp + 0.005, 0.3, 1e-3, SUN_HIGH, scale=2.0 ** -40),
+        # (a distance of 2^31 would do as well, but every value along such a ray is NaN; a negative distance marches backwards
+        # to finite values, so the spoiler's own lane says something too)
+        "lean": ray64(B, B.Rp + 0.005, 0.3, -1e-3, SUN_HIGH),
+        "extLean": ray64(B, 0.5 * (B.leanFloor + B.extFloor), 1.0, 1e-3, SUN_HIGH),
+        "firstStepOnly": ray64(B, B.Rp + 0.005, 0.3, 32e-9, SUN_HIGH),
+        "belowOzone": ray64(B, low, 1.0, B.Rp + 0.020 - low, SUN_HIGH),
+        "inner": ray64(B, low, 1.0, mid - low, SUN_HIGH),
+        "sunClear": ray64(B, B.Rp + 0.005, 0.3, 1e-3, -0.3),
+    }
+    return {k: v.astype(np.float32) for k, v in s.items()}
+
+
+# what a spoiler's failure drags along by construction, on any block: a direction outside the length range fails `lean` by the
+# same term; a negative distance is a negative step; a far end above the INNER ceiling is above the ozone bound; a sun below
+# the horizon is not positive
+SPOILER_COUPLED = {
+    "setupLean": {"lean"},
+    "lean": {"firstStepOnly"},
+    "extLean": set(),
+    "firstStepOnly": set(),
+    "belowOzone": set(),
+    "inner": {"belowOzone"},
+    "sunClear": {"sunPositive", "sunAboveHorizon"},
+}
+
+
+def setup_families(B, only=None):
+    """The families of the set-up gates. `only`: a subset of family names (the block and LUT variants run four gates)."""
+    lf, ef, ec, ic, oz = B.leanFloor, B.extFloor, B.extCeil, B.innerCeil, B.ozoneLow
+    h5 = B.Rp + 0.005
+    # The lean floor is where the densities exp(-altitude / H) reach e^80; 0.08 % of the radius further down they reach e^84 and
+    # shortly after overflow, which makes every value NaN. The sweeps across the floor stop there on the failing side instead
+    # of at the relative distance 2^-6: 0.16 % of the squared radius, still beyond the census's 2^-10.
+    deep = 1.0 - 0.0008
+    specs = [
+        # setupLean -------------------------------------------------------------------------------------------------------
+        # (an origin at the lean floor has its closest approach there too: rmin2 <= r2)
+        ("setupLean/origin-radius", "setupLean", lambda x: ray64(B, x, 1.0, 1e-3, SUN_HIGH), "origin2", lf * lf, deep * lf, 1.03 * lf,
+         "setupLean", {"lean"}),
+        # (leanLength2(direction2) is a term of both)
+        ("setupLean/direction2-2^-60", "setupLean", lambda x: ray64(B, h5, 0.3, 1e-3, SUN_HIGH, scale=x), "direction2", 2.0 ** -60,
+         2.0 ** -31, 2.0 ** -29, "setupLean", {"lean"}),
+        ("setupLean/direction2-2^60", "setupLean", lambda x: ray64(B, h5, 0.3, 1e-3, SUN_HIGH, scale=x), "direction2", 2.0 ** 60,
+         2.0 ** 29, 2.0 ** 31, "setupLean", {"lean"}),
+        # lean ------------------------------------------------------------------------------------------------------------
+        # closest approach inside the segment (t* = 0.3 r < D): a ray from outside the shell that dips to the lean floor
+        ("lean/rmin2-tstar-inside", "lean", lambda x: ray64(B, x, -0.3, 4.0, SUN_HIGH), "rmin2", lf * lf,
+         deep * lf / math.sqrt(1.0 - 0.09), 1.1 * lf, "lean"),
+        # ... and outside (steeply down, t* = 0.9 r): the far end is the closest point
+        ("lean/rmin2-tstar-outside", "lean", lambda x: ray64(B, 1.01 * lf, -0.9, x, SUN_HIGH), "rmin2", lf * lf, 0.01,
+         0.909 * lf - math.sqrt((0.909 * lf) ** 2 - (1.01 * lf) ** 2 + (deep * lf) ** 2), "lean"),
+        ("lean/distance-2^30", "lean", lambda x: ray64(B, h5, 0.3, x, SUN_HIGH), "D", 2.0 ** 30, 2.0 ** 29, 2.0 ** 31, "lean"),
+        # (origin2 <= 2^60 of setupLean is the same bound)
+        ("lean/radius-2^30", "lean", lambda x: ray64(B, x, 1.0, 1e-3, SUN_HIGH), "radius", 2.0 ** 30, 2.0 ** 29, 2.0 ** 31, "lean",
+         {"setupLean"}),
+        # extLean ---------------------------------------------------------------------------------------------------------
+        ("extLean/rmin2-floor", "extLean", lambda x: ray64(B, x, 1.0, 1e-3, SUN_HIGH), "rmin2", ef * ef, 0.995 * ef, 1.005 * ef,
+         "extLean"),
+        # (the INNER ceiling lies 2^-9 below the extinction ceiling on Earth: the sparse points pass it)
+        ("extLean/ceiling-by-origin", "extLean", lambda x: ray64(B, x, -0.9, 0.01, SUN_HIGH), "maxr2", ec * ec, 0.995 * ec, 1.005 * ec,
+         "extLean", {"inner"}),
+        ("extLean/ceiling-by-far-end", "extLean", lambda x: ray64(B, ic - 0.0137, 1.0, x, SUN_HIGH), "maxr2", ec * ec, 0.002,
+         0.06, "extLean", {"inner"}),
+        # firstStepOnly ---------------------------------------------------------------------------------------------------
+        ("firstStepOnly/dS-1e-7", "firstStepOnly", lambda x: ray64(B, h5, 0.3, x, SUN_HIGH), "dS", float(np.float32(0.0000001)),
+         1.6e-6, 6.4e-6, "firstStepOnly"),
+        # belowOzone ------------------------------------------------------------------------------------------------------
+        ("belowOzone/by-origin", "belowOzone", lambda x: ray64(B, x, -0.9, 0.002, SUN_HIGH), "maxr2", oz * oz, 0.996 * oz, 1.004 * oz,
+         "belowOzone"),
+        ("belowOzone/by-far-end", "belowOzone", lambda x: ray64(B, B.Rp + 0.001, 1.0, x, SUN_HIGH), "maxr2", oz * oz, 0.0002, 0.034,
+         "belowOzone"),
+        # INNER -----------------------------------------------------------------------------------------------------------
+        ("inner/by-origin", "inner", lambda x: ray64(B, x, -0.9, 0.01, SUN_HIGH), "maxr2", ic * ic, 0.996 * ic, 1.004 * ic, "inner",
+         {"extLean"}),
+        ("inner/by-far-end", "inner", lambda x: ray64(B, ic - 0.0137, 1.0, x, SUN_HIGH), "maxr2", ic * ic, 0.002, 0.04, "inner",
+         {"extLean"}),
+        # sunClear --------------------------------------------------------------------------------------------------------
+        ("sunClear/margin", "sunClear", lambda x: ray64(B, h5, 0.3, 1e-3, x), "r_musun",
+         census(ray64(B, h5, 0.3, 1e-3, 0.05), B)["q"]["clearThreshold"], 0.002, 0.1, "sunClear"),
+        # The margin matters where the horizon is not depressed: at 5 km altitude its cosine is -0.04 and a sun cosine above 0
+        # clears it with the whole disc anyway. 500 m below the ground the horizon cosine is 0, and a sun cosine between 0 and
+        # sin R = 0.0093 leaves the disc cut: the rays of this sweep below the threshold have a smoothstep below 1.
+        ("sunClear/margin-ground", "sunClear", lambda x: ray64(B, B.Rp - 0.0005, 0.3, 1e-3, x), "r_musun",
+         census(ray64(B, B.Rp - 0.0005, 0.3, 1e-3, 0.05), B)["q"]["clearThreshold"], 0.002, 0.1, "sunClear"),
+        # (sunClear contains the sign test)
+        ("sunClear/r_musun-0", "sunPositive", lambda x: ray64(B, h5, 0.3, 1e-3, x), "r_musun", 0.0, -0.05, 0.05, "sunClear",
+         {"sunClear"}),
+    ]
+    out = []
+    for spec in specs:
+        name, gate, make, quantity, thr, lo, hi, spoiler = spec[:8]
+        coupled = spec[8] if len(spec) > 8 else ()
+        if only is not None and name not in only:
+            continue
+        scale = None
+        if quantity == "r_musun":
+            # a dot product of the origin: its float32 steps are those of the origin's components, ulps of the radius
+            scale =census(make(0.5 * (lo + hi)), B)["q"]["radius"]
+        out.append(_sweep(B, name, gate, make, quantity, thr, lo, hi, spoiler, coupled, scale))
+    # The 9.9 km bound stands 100 m below the foot of the ozone tent. A bound that is off by a few hundred metres lies between
+    # the sparse points of the two sweeps above, so: far ends from 6 to 14 km in steps of 62 m, upwards from 1 km.
+    if only is None or "belowOzone/foot-of-tent" in only:
+        xs = list(np.linspace(0.005, 0.013, 129))
+        out.append(Family("belowOzone/foot-of-tent", "belowOzone", "range", xs,
+                          [ray64(B, B.Rp + 0.001, 1.0, x, SUN_HIGH) for x in xs], "belowOzone"))
+    # Whether a step with t < 1e-7 tells 1 from the quotient of the two taps is a matter of one rounding: 0.1 mm from the
+    # origin the tap T_end differs from T_origin only where (r mu + t) / r rounds differently from mu. So: 64 orientations
+    # (view cosine, azimuth, sun cosine), each with dS = 0.5e-7 (step 1 lies below 1e-7) in the first half of the family and
+    # with dS = 2e-7 in the second.
+    if only is None or "firstStepOnly/orientations" in only:
+        xs, rays = [], []
+        for dS in (0.5e-7, 2e-7):
+            for k in range(64):
+                xs.append((dS, k))
+                rays.append(ray64(B, B.Rp + 0.0005 + 0.00007 * k, -0.95 + 0.03 * k, 32.0 * dS, 0.2 + 0.012 * k, az=0.37 * k))
+        out.append(Family("firstStepOnly/orientations", "firstStepOnly", "range", xs, rays, "firstStepOnly"))
+    if only is None:
+        # far above the extinction ceiling the densities become denormal and then 0: lean rays (any radius below 2^30 is) whose
+        # extinction is no operand for the lean division, which extLean must keep away from it. Upwards from 100 km, the far
+        # end from 500 to 1300 km.
+        xs = list(np.linspace(0.4, 1.2, 97))
+        out.append(Family("extLean/thin-air", None, "range", xs, [ray64(B, B.Rp + 0.1, 1.0, x, SUN_HIGH) for x in xs], "extLean"))
+        values = [0.0, -0.0, -1e-3, -1e-30, float("inf"), 3.0e38, float("nan"), 1e-3]
+        out.append(Family("lean/distance-points", "lean", "points", values, [ray64(B, h5, 0.3, v, SUN_HIGH) for v in values], "lean"))
+        # negative distances march backwards: t <= 0 at every step, which the bound behind sunClear (numerator >= r_musun for
+        # t >= 0) does not cover. Straight up with the sun just above the sunClear threshold, and an ordinary slanted ray, from
+        # 1 mm to 90 km backwards (the far end stays above the lean floor)
+        xs = [-x for x in np.geomspace(1e-6, 0.09, 48)]
+        rays = [ray64(B, h5, 1.0, x, 0.0135) for x in xs] + [ray64(B, h5, 0.3, x, SUN_HIGH) for x in xs]
+        out.append(Family("lean/negative-distances", None, "range", xs + xs, rays, "lean"))
+    return out
+
+
+# Families whose values cannot tell their rays apart, by the nature of the march and not of the sweep:
+# * beyond a radius or a distance of 2^30 Mm every sample lies where both densities underflow to 0, the extinction is 0 and
+#   the in-scatter integral (1 - T) / extinction is 0 / 0: every value on both sides of the threshold is NaN;
+# * steps of 2^-45 Mm are shorter than the LUT can tell apart: the segment transmittance is a ratio of two equal taps,
+#   1 - T is 0 and so is every value.
+# The equality rule still holds them to a NaN for a NaN and a +0 for a +0 on either side of their gates.
+ALL_NAN = ("lean/distance-2^30", "lean/radius-2^30")
+ALL_ZERO = ("step/segment2-axis", "step/segment2-general")
+
+VARIANT_FAMILIES = ("firstStepOnly/dS-1e-7", "belowOzone/by-origin", "belowOzone/by-far-end", "inner/by-origin", "inner/by-far-end",
+                    "sunClear/margin", "sunClear/margin-ground", "sunClear/r_musun-0", "belowOzone/foot-of-tent",
+                    "firstStepOnly/orientations")
+
+
+def step_families(B):
+    """Families for the gates taken again at every step of marchLoop."""
+    h5 = B.Rp + 0.005
+    out = []
+    # the sun sets part-way: a long level ray heading away from the sun (az = 0), the sun cosine at its origin from below the
+    # horizon to well above it
+    xs = list(np.linspace(-0.06, 0.10, 161))
+    out.append(Family("step/sunset", None, "range", xs, [ray64(B, B.Rp + 0.003, 0.0, 0.25, x, az=0.0) for x in xs], "sunClear"))
+
+    # segment2 across 2^-90. With the origin on one axis and the direction on another the steps (0, -dS, 0) are exact and
+    # segment2 = dS^2 does cross; on a general ray every step rounds onto the origin and the segment is 0
+    def axis(x):
+        return np.array([0.0, h5, 0.0, 1.0, 0.0, 0.0, x])
+
+    out.append(_sweep(B, "step/segment2-axis", "segmentNominal", axis, lambda r: (r[6] / 32.0) ** 2, 2.0 ** -90, 2.0 ** -41,
+                      2.0 ** -39, "lean", {"firstStepOnly"}))
+    out.append(_sweep(B, "step/segment2-general", "segmentNominal", lambda x: ray64(B, h5, 0.3, x, SUN_HIGH),
+                      lambda r: (r[6] / 32.0) ** 2, 2.0 ** -90, 2.0 ** -41, 2.0 ** -39, "lean", {"firstStepOnly"}))
+    # noOzone: marches that enter and leave the 10 - 40 km tent, upwards from 4 km and downwards from 50 km
+    xs = list(np.geomspace(0.002, 0.06, 96))
+    out.append(Family("step/ozone-up", None, "range", xs, [ray64(B, B.Rp + 0.004, 1.0, x, SUN_HIGH) for x in xs], "belowOzone"))
+    xs = list(np.geomspace(0.002, 0.048, 96))
+    out.append(Family("step/ozone-down", None, "range", xs, [ray64(B, B.Rp + 0.050, -1.0, x, SUN_HIGH) for x in xs], "belowOzone"))
+    xs = list(np.geomspace(0.004, 0.3, 96))
+    out.append(Family("step/ozone-slant", None, "range", xs, [ray64(B, B.Rp + 0.002, 0.15, x, SUN_HIGH) for x in xs], "belowOzone"))
+    # LUT right edge: the sun tap's column is the last one when the sun is at or below the geometric horizon of the sample
+    out.append(_sweep(B, "step/lut-right-edge", "sunAboveHorizon", lambda x: ray64(B, h5, 0.3, 1e-3, x),
+                      lambda r: census(r, B)["q"]["mu_sun"] - census(r, B)["q"]["horizon"], 0.0, -0.09, -0.005, "inner",
+                      {"sunClear", "sunPositive"}, scale=1.0))
+    return out
+
+
+def random_rays(B, n=8010, seed=0x5A2C):
+    """Seeded rays: origins from 100 km below the ground to outside the shell, any direction (non-unit and zero-length
+    included), distances log-uniform over 1e-12 .. 1e3."""
+    rng = np.random.default_rng(seed)
+    r = rng.uniform(B.Rp - 0.1, B.Ra + 0.1, n)
+    up = rng.normal(size=(n, 3))
+    up /= np.linalg.norm(up, axis=1, keepdims=True)
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    kind = rng.integers(0, 100, n)
+    scale = np.ones(n)
+    scale[kind < 30] = 10.0 ** rng.uniform(-3, 3, int((kind < 30).sum()))
+    scale[kind == 30] = 0.0
+    scale[kind == 31] = 2.0 ** -40
+    scale[kind == 32] = 2.0 ** 40
+    # a third of the rays look along the local vertical or the horizon, where the closest approach and the far end decide
+    snap = rng.integers(0, 6, n)
+    d[snap == 0] = up[snap == 0]
+    d[snap == 1] = -up[snap == 1]
+    D = 10.0 ** rng.uniform(-12, 3, n)
+    rays = np.concatenate([r[:, None] * up, scale[:, None] * d, D[:, None]], axis=1)
+    return Family("random", None, "random", list(range(n)), rays, "lean")
+
+
+def random_shuffles(n, seed=0x5A2C):
+    return [np.random.default_rng(seed + 1 + k).permutation(n) for k in range(3)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Wave forms
+# ---------------------------------------------------------------------------------------------------------------------------
+class Layout:
+    """idx[slot]: index of the slot's ray among the family's K rays (K = the spoiler); hole[slot]; forms: (name, first wave,
+    waves). The slots are those of ONE launch: wave w = slots 64 w .. 64 w + 63, the last wave cut short."""
+
+    def __init__(self):
+        self.idx, self.hole, self.forms = [], [], []
+
+    def add(self, name, idx, hole=None):
+        idx = np.asarray(idx, np.int64)
+        assert len(self.slots()) % 64 == 0, "only the last form may end inside a wave"
+        self.forms.append((name, len(self.slots()) // 64, (len(idx) + 63) // 64))
+        self.idx.append(idx)
+        self.hole.append(np.zeros(len(idx), bool) if hole is None else np.asarray(hole, bool))
+
+    def slots(self):
+        return np.concatenate(self.idx) if self.idx else np.zeros(0, np.int64)
+
+    def holes(self):
+        return np.concatenate(self.hole)
+
+    def form_of(self, slot):
+        wave = slot // 64
+        for name, first, waves in self.forms:
+            if first <= wave < first + waves:
+                return name, wave - first
+        raise IndexError(slot)
+
+
+def windows(K):
+    """First rays of the natural windows: 64 consecutive rays, sliding by 16 (a family shorter than 64 wraps around)."""
+    if K <= 64:
+        return [0]
+    starts = list(range(0, K - 64, 16))
+    return starts + [K - 64]
+
+
+def layout(K):
+    """All wave forms of a family of K rays (indices 0 .. K - 1; K is the spoiler)."""
+    lane = np.arange(64)
+    L = Layout()
+    uniform = np.repeat(np.arange(K), 64)
+    L.add("uniform", uniform)
+    spoiled = uniform.copy()
+    for k in range(K):
+        spoiled[64 * k + SPOILER_LANES[k % 3]] = K
+    L.add("spoiled", spoiled)
+    natural = np.concatenate([(s + lane) % K for s in windows(K)])
+    L.add("natural", natural)
+    single = np.ones(64 * K, bool)
+    for k in range(K):
+        single[64 * k + (7 * k) % 64] = False
+    L.add("single", uniform, single)
+    holes = np.tile(lane % 3 == 2, len(windows(K)))
+    L.add("holes", natural[:-23], holes[:-23])
+    return L
+
+
+def random_layout(n, shuffles):
+    L = Layout()
+    for k, perm in enumerate(shuffles):
+        idx = np.concatenate([perm, perm[: (-len(perm)) % 64]]) if k + 1 < len(shuffles) else perm
+        L.add("shuffle%d" % k, idx)
+    return L
+
+
+def launch_rays(rays, spoiler, lay):
+    """The 8-dword rays of a launch: the family's rays (and its spoiler at index K) in the layout's slots."""
+    table = np.concatenate([rays, spoiler[None, :]]).astype(np.float32)
+    out = np.zeros((len(lay.slots()), 8), np.uint32)
+    out[:, :7] = table[lay.slots()].view(np.uint32)
+    out[:, 7] = np.where(lay.holes(), HOLE, 0)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Blocks, LUTs and the oracle
+# ---------------------------------------------------------------------------------------------------------------------------
+def earth(elevation=30.0):
+    from syzygy_amd import scene
+
+    return scene.atmosphere_packed(scene.default_atmosphere(scene.sun_euler_for_elevation(elevation)))
+
+
+class Variant:
+    """A block and LUT variant: the packed block, the LUT extent, a texel to overwrite, and the flags the device must read."""
+
+    def __init__(self, name, atm, extent=BASE_EXTENT, poke=None, rows_interior=None, **flags):
+        self.name, self.atm, self.extent, self.poke = name, atm, extent, poke
+        # TLut::rowsInterior behind k_frame_prep, where a test relies on its value: read from the device, written down here
+        self.rows_interior = rows_interior
+        self.flags = dict(lean=1, signClearCoefficients=1, zeroAbsorptionRayleigh=1, zeroScatteringOzone=1, extModerate=1, moderate=1)
+        self.flags.update(flags)
+
+    def bounds(self):
+        return Bounds(self.atm)
+
+    def lut(self):
+        from oracle import binding as ob
+
+        t = ob.transmittance_lut(self.atm, self.extent[0], self.extent[1], threads=8)
+        if self.poke is not None:
+            row, col, channel, value = self.poke
+            t[row, col, channel] = value
+        return t
+
+
+def _edited(**fields):
+    atm = copy.deepcopy(earth())
+    for k, v in fields.items():
+        if isinstance(v, tuple):
+            getattr(atm, k)[:] = v
+        else:
+            setattr(atm, k, v)
+    return atm
+
+
+VARIANT_NAMES = ("earth", "rayleigh-absorption", "ozone-scattering", "negative-coefficient", "thin-density-scale", "lut-texel-2^-60",
+                 "lut-256x64", "lut-33x7", "lut-33x25", "sun-70", "sun-5", "sun--3")
+
+
+def variants():
+    """The blocks and LUTs, in the order of VARIANT_NAMES (tests/test_march_rays.py holds the two equal)."""
+    e = earth()
+    return [
+        Variant("earth", e),
+        Variant("rayleigh-absorption", _edited(absorptionRayleighPerMm=(0.1, 0.2, 0.3)), zeroAbsorptionRayleigh=0),
+        Variant("ozone-scattering", _edited(scatteringOzonePerMm=(0.05, 0.1, 0.02)), zeroScatteringOzone=0),
+        Variant("negative-coefficient", _edited(absorptionRayleighPerMm=(0.0, -0.01, 0.0)), signClearCoefficients=0,
+                zeroAbsorptionRayleigh=0, zeroScatteringOzone=0, extModerate=0),
+        Variant("thin-density-scale", _edited(densityScaleMieMm=float(e.planetRadiusMm) * 2.0 ** -19), lean=0, extModerate=0),
+        # (rows 8 and 9, columns 14 and 15 of the 128 x 32 LUT are the view taps of the rays at 5 km altitude with mu = 0.3)
+        Variant("lut-texel-2^-60", e, poke=(9, 14, 1, 2.0 ** -60), moderate=0),
+        Variant("lut-256x64", e, extent=(256, 64), rows_interior=1),
+        Variant("lut-33x7", e, extent=(33, 7), rows_interior=1),
+        # (256, 64) and (33, 7) read the same rowsInterior, set; with 25 rows the v coordinate of the lowest radius,
+        # fma(fl(0.5 / 25), 25, -0.5), comes out below 0 and k_frame_prep leaves the flag clear
+        Variant("lut-33x25", e, extent=(33, 25), rows_interior=0),
+        Variant("sun-70", earth(70.0)),
+        Variant("sun-5", earth(5.0)),
+        Variant("sun--3", earth(-3.0)),
+    ]
+
+
+def oracle_values(atm, lut, rays):
+    """oracle_scattering_integral of each ray ([n, 7] float32) -> [n, 3] float32."""
+    from oracle import binding as ob
+
+    h = ob.lib()
+    rays = np.ascontiguousarray(rays, np.float32)
+    out = np.zeros((len(rays), 3), np.float32)
+    lut = np.ascontiguousarray(lut, np.float32)
+    FP = C.POINTER(C.c_float)
+    base_r, base_o, pl = rays.ctypes.data, out.ctypes.data, ob.fptr(lut)
+    W, H = lut.shape[1], lut.shape[0]
+    ref = C.byref(atm)
+    fn = h.oracle_scattering_integral
+    for i in range(len(rays)):
+        fn(ref, pl, W, H, C.cast(base_r + 28 * i, FP), C.cast(base_r + 28 * i + 12, FP), float(rays[i, 6]), C.cast(base_o + 12 * i, FP))
+    return out
+
+
+def same_bits(got, want):
+    """Per float: bit-identical (sign of zero included), or NaN for NaN."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    return (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))

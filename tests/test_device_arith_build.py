@@ -27,8 +27,9 @@ def test_devarith_flags_are_the_product_hipflags():
     assert "--offload-arch=gfx950" in want and "-ffp-contract=off" in want
     assert tests["DEVARITH_FLAGS"][1].split() == want
     rule = open(os.path.join(HERE, "cpp", "Makefile")).read()
-    recipe = re.search(r"^libszg_devarith\.so:.*\n\t(.*)$", rule, re.M).group(1)
-    assert "$(DEVARITH_FLAGS)" in recipe and not re.search(r"\s-(O\d|f|m|std|-offload)", recipe.replace("$(DEVARITH_FLAGS)", ""))
+    for target in ("libszg_devarith", "libszg_marchrays"):
+        recipe = re.search(r"^%s\.so:.*\n\t(.*)$" % target, rule, re.M).group(1)
+        assert "$(DEVARITH_FLAGS)" in recipe and not re.search(r"\s-(O\d|f|m|std|-offload)", recipe.replace("$(DEVARITH_FLAGS)", ""))
 
 
 def test_devarith_library_builds_for_gfx950():
@@ -37,4 +38,14 @@ def test_devarith_library_builds_for_gfx950():
     data = open(path, "rb").read()
     assert b"gfx950" in data
     for name in (b"szg_da_sweep", b"szg_da_eval", b"szg_da_unpack_half4", b"szg_da_pack_half4_mul", b"szg_da_pack_half_range"):
+        assert name in data, name
+
+
+def test_marchrays_library_builds_for_gfx950():
+    """tests/cpp/libszg_marchrays.so (tests/test_gpu_march_rays.py): the product's kernels_lut.hip compiles inside the harness's
+    translation unit, and the march kernels of both configurations are in the code object."""
+    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libszg_marchrays.so"], check=True)
+    data = open(os.path.join(HERE, "cpp", "libszg_marchrays.so"), "rb").read()
+    assert b"gfx950" in data
+    for name in (b"szg_mr_run", b"k_march_rays", b"k_march_flags", b"k_frame_prep", b"k_lut_range"):
         assert name in data, name
