@@ -1,6 +1,6 @@
 // devarith.hip — test infrastructure: the device arithmetic of include/szg/fpmath.h (its __HIP_DEVICE_COMPILE__ branches)
 // and syzygy_amd/csrc/szg_device.hpp (the lean operators, the store formats), evaluated ON THE GPU over whole domains and
-// compared with references computed on the GPU in float64. Built with the product's HIPFLAGS (tests/cpp/Makefile; the flag
+// compared with references computed on the GPU in float64. Built with the product's HIPFLAGS (tests/Makefile; the flag
 // line is checked by tests/test_device_arith_build.py) so that it measures the code the kernels run. Driven through ctypes by
 // tests/test_gpu_device_arith.py.
 //

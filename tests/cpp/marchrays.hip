@@ -1,7 +1,7 @@
 // marchrays.hip — test infrastructure: scatteringIntegral / marchLoop of syzygy_amd/csrc/szg_device.hpp called RAY BY RAY on
 // the GPU, one thread per ray, so that a test decides which rays share a wave (tests/march_rays.py lays the waves out,
 // tests/test_gpu_march_rays.py compares every lane with the oracle's scalar march bit for bit). Built with the product's
-// HIPFLAGS (tests/cpp/Makefile; the flag line is checked by tests/test_device_arith_build.py).
+// HIPFLAGS (tests/Makefile; the flag line is checked by tests/test_device_arith_build.py).
 //
 // The product's own kernels_lut.hip is part of this translation unit: the FramePrep block of the `prepped` configuration
 // comes from its k_frame_prep and the LUT's status dword from its k_lut_range, through its launch functions; nothing of

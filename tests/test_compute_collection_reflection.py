@@ -14,6 +14,7 @@ import pytest
 
 from syzygy_amd import abi, lib, library_path, pipelines
 from tests import compute_collection_model as model
+from tests import native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "compute_collection_reflection.json")
@@ -141,12 +142,7 @@ def test_cpp_accessors_agree_with_the_reflection_of_the_binaries(golden, tmp_pat
     import subprocess
 
     lib()  # built and loadable
-    exe = str(tmp_path / "compute_collection_reflection")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "compute_collection_reflection.cpp"), "-o", exe, "-L" + csrc, "-lszg_hip",
-                    "-Wl,-rpath," + csrc], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([native.build("cpp/compute_collection_reflection")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     got = json.loads(r.stdout)
     assert (got["valid"], got["count"], got["index"]) == (1, len(golden), 0)

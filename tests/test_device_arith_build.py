@@ -1,11 +1,15 @@
-"""tests/cpp/libszg_devarith.so, the library behind tests/test_gpu_device_arith.py: it cross-compiles for gfx950 without a GPU,
-and it is compiled with the product's HIPFLAGS (a sweep of code built with other flags says nothing about the kernels)."""
+"""The test libraries around the product's device code - tests/cpp/libszg_devarith.so (tests/test_gpu_device_arith.py),
+tests/cpp/libszg_marchrays.so (tests/test_gpu_march_rays.py), tests/mipsample/libszg_mipsample.so (tests/test_gpu_mipmaps.py):
+they cross-compile for gfx950 without a GPU, and they are compiled with the product's HIPFLAGS (a sweep of code built with
+other flags says nothing about the kernels)."""
 import os
 import re
-import subprocess
+
+from tests import native
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
+LIBRARIES = ("cpp/libszg_devarith.so", "cpp/libszg_marchrays.so", "mipsample/libszg_mipsample.so")
 
 
 def _assignments(path):
@@ -20,22 +24,26 @@ def _assignments(path):
 
 def test_devarith_flags_are_the_product_hipflags():
     product = _assignments(os.path.join(ROOT, "syzygy_amd", "csrc", "Makefile"))
-    tests = _assignments(os.path.join(HERE, "cpp", "Makefile"))
+    tests = _assignments(os.path.join(HERE, "Makefile"))
     op, hipflags = product["HIPFLAGS"]
     assert op == "?="
     want = hipflags.replace("$(ARCH)", product["ARCH"][1]).split()
     assert "--offload-arch=gfx950" in want and "-ffp-contract=off" in want
-    assert tests["DEVARITH_FLAGS"][1].split() == want
-    rule = open(os.path.join(HERE, "cpp", "Makefile")).read()
-    for target in ("libszg_devarith", "libszg_marchrays"):
-        recipe = re.search(r"^%s\.so:.*\n\t(.*)$" % target, rule, re.M).group(1)
-        assert "$(DEVARITH_FLAGS)" in recipe and not re.search(r"\s-(O\d|f|m|std|-offload)", recipe.replace("$(DEVARITH_FLAGS)", ""))
+    assert tests["DEVICE_FLAGS"][1].split() == want
+    assert tests["DEVICE_LIBS"][1].split() == list(LIBRARIES)
+    rule = open(os.path.join(HERE, "Makefile")).read()
+    # the three are built by the one pattern rule, which adds no flag of its own
+    assert not re.search(r"^[^#\n]*libszg_(devarith|marchrays|mipsample)\.so.*:", rule, re.M)
+    recipe = re.search(r"^libszg_%\.so:.*\n\t(.*)$", rule, re.M).group(1)
+    assert "$(DEVICE_FLAGS)" in recipe and not re.search(r"\s-(O\d|f|m|std|-offload)", recipe.replace("$(DEVICE_FLAGS)", ""))
+    for target in LIBRARIES:  # and what make then runs: the compiler, the product's flags, and no such flag after them
+        (command,) = native.commands(target)
+        words = command.split()
+        assert words[1:1 + len(want)] == want and not [w for w in words[1 + len(want):] if re.match(r"-(O\d|f|m|std|-offload)", w)]
 
 
 def test_devarith_library_builds_for_gfx950():
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libszg_devarith.so"], check=True)
-    path = os.path.join(HERE, "cpp", "libszg_devarith.so")
-    data = open(path, "rb").read()
+    data = open(native.build("cpp/libszg_devarith.so"), "rb").read()
     assert b"gfx950" in data
     for name in (b"szg_da_sweep", b"szg_da_eval", b"szg_da_unpack_half4", b"szg_da_pack_half4_mul", b"szg_da_pack_half_range"):
         assert name in data, name
@@ -44,8 +52,13 @@ def test_devarith_library_builds_for_gfx950():
 def test_marchrays_library_builds_for_gfx950():
     """tests/cpp/libszg_marchrays.so (tests/test_gpu_march_rays.py): the product's kernels_lut.hip compiles inside the harness's
     translation unit, and the march kernels of both configurations are in the code object."""
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libszg_marchrays.so"], check=True)
-    data = open(os.path.join(HERE, "cpp", "libszg_marchrays.so"), "rb").read()
+    data = open(native.build("cpp/libszg_marchrays.so"), "rb").read()
     assert b"gfx950" in data
     for name in (b"szg_mr_run", b"k_march_rays", b"k_march_flags", b"k_frame_prep", b"k_lut_range"):
         assert name in data, name
+
+
+def test_mipsample_library_builds_for_gfx950():
+    """tests/mipsample/libszg_mipsample.so (tests/test_gpu_mipmaps.py): the product's szg_texture.hpp inside a test-only kernel."""
+    data = open(native.build("mipsample/libszg_mipsample.so"), "rb").read()
+    assert b"gfx950" in data and b"szg_mipsample" in data

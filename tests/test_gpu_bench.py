@@ -8,6 +8,8 @@ import sys
 
 import pytest
 
+from tests import native
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -95,8 +97,7 @@ def test_n_rank_frame_through_the_c_abi_collectives_on_one_gpu(ranks, no_gather)
     same entry points, same in-place / root-only contracts, bytes staged through a mapped file. Everything above that
     boundary is the product's code: the communicator pair, byte offsets of tiles and LUT slices, the cyclic row blocks, the
     two frames in flight, the compose. The composed 8K image must have the checksum of the single-GPU frame."""
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "libmock_rccl.so"], check=True)
-    env = {"SZG_RCCL_LIBRARY": os.path.join(ROOT, "tests", "cpp", "libmock_rccl.so")}
+    env = {"SZG_RCCL_LIBRARY": native.build("cpp/libmock_rccl.so")}
     if no_gather:  # szg_rowtile_gather's grouped ncclSend / ncclRecv form (what a library without ncclGather gets)
         env["SZG_RCCL_NO_GATHER"] = "1"
     many = _run([sys.executable, "bench.py", "--gpus", str(ranks), "--backend", "nccl", "--same-device", "--steps", "2", "--warmup", "1",

@@ -2,7 +2,6 @@
 here with hipcc (tests/cpp/record_draw_compute_collection.cpp). With COMPUTE_COLLECTION the scene colour is the model's image
 of the current program (spill beyond the subregion included) and a poisoned G-buffer and depth image keep every byte; switched
 back to DEFERRED the frame equals the frame of a renderer that never switched; selectShader(7) changes nothing."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,25 +9,19 @@ import pytest
 
 from syzygy_amd import abi, lib
 from tests import compute_collection_model as model
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
+def exe():
     import torch
 
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    out = str(tmp_path_factory.mktemp("cpp") / "record_draw_compute_collection")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(HERE, "cpp", "record_draw_compute_collection.cpp"), "-o", out, "-L" + csrc, "-lszg_hip",
-                    "-Wl,-rpath," + csrc], check=True)
-    return out
+    return native.build("cpp/record_draw_compute_collection")
 
 
 @pytest.mark.parametrize("extent,texture", [((320, 180), (320, 180)), ((500, 300), (640, 360))], ids=["whole", "subregion"])

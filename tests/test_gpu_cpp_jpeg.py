@@ -1,10 +1,9 @@
 """The C++ mirror of include/szg/jpeg.h (include/szg/assets.hpp) through its own interface, from a program built with hipcc by
-tests/jpeg/Makefile (load_jpeg_gltf.cpp): AssetLibrary::loadGLTFFromPath(path, SZG_GLTF_JPEG_FOR_DEVICE) reconstructs the
+tests/Makefile (jpeg/load_jpeg_gltf.cpp): AssetLibrary::loadGLTFFromPath(path, SZG_GLTF_JPEG_FOR_DEVICE) reconstructs the
 JPEG maps of a glTF file on the GPU, ORM overrides as masks, with the mip chain behind; loadTextureFromPath decodes a JPEG
 file only with setDecodeJPEG."""
 import base64
 import json
-import os
 import subprocess
 
 import numpy as np
@@ -14,9 +13,9 @@ from syzygy_amd import lib
 from tests import gltf_writer as gw
 from tests import jpeg_fixtures as jf
 from tests import mipmap_model as mm
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def test_asset_library_reconstructs_jpeg_maps_on_the_device(tmp_path):
@@ -25,7 +24,7 @@ def test_asset_library_reconstructs_jpeg_maps_on_the_device(tmp_path):
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "jpeg"), "load_jpeg_gltf"], check=True)
+    exe = native.build("jpeg/load_jpeg_gltf")
     color, mr, file_name = "420_33x31_prog_q92", "422_17x9_base_q92", "h1v2_33x33_base_q85"
     b = gw.GltfBuilder()
     png = np.random.default_rng(2).integers(0, 256, (5, 6, 4), dtype=np.uint8)
@@ -38,7 +37,7 @@ def test_asset_library_reconstructs_jpeg_maps_on_the_device(tmp_path):
     gltf.write_bytes(json.dumps(b.document()).encode().replace(b'"buffers": [{"byteLength": 0}]', b'"buffers": []'))
     jpg = tmp_path / "file.jpg"
     jpg.write_bytes(jf.data(file_name))
-    p = subprocess.run([os.path.join(HERE, "jpeg", "load_jpeg_gltf"), str(gltf), str(tmp_path / "out"), str(jpg)], capture_output=True,
+    p = subprocess.run([exe, str(gltf), str(tmp_path / "out"), str(jpg)], capture_output=True,
                        text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = p.stdout.strip().splitlines()

@@ -2,7 +2,6 @@
 built with hipcc (tests/cpp/asset_library_mips.cpp): an AssetLibrary with the generateMips switch on owns chains for what it
 loads, textureMips() lists them, DeferredShadingPipeline::setTextureMips takes them, and the chain of a loaded PNG equals the
 model's."""
-import os
 import subprocess
 
 import numpy as np
@@ -11,10 +10,9 @@ import pytest
 from syzygy_amd import lib
 from tests import gltf_writer
 from tests import mipmap_model as mm
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 def test_asset_library_builds_lists_and_registers_chains(tmp_path):
@@ -23,11 +21,7 @@ def test_asset_library_builds_lists_and_registers_chains(tmp_path):
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    exe = str(tmp_path / "asset_library_mips")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(HERE, "cpp", "asset_library_mips.cpp"), "-o", exe, "-L" + csrc, "-lszg_hip", "-Wl,-rpath," + csrc],
-                   check=True)
+    exe = native.build("cpp/asset_library_mips")
     w, h = 37, 19
     rgba = np.random.default_rng(9).integers(0, 256, (h, w, 4), dtype=np.uint8)
     png = tmp_path / "noise.png"

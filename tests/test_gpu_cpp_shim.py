@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests import native
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,9 +20,7 @@ def test_cpp_record_draw_matches_oracle(tmp_path):
     from oracle import binding as ob
     from syzygy_amd import abi, lib, scene
 
-    exe = os.path.join(HERE, "cpp", "record_draw")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(HERE, "cpp")], check=True)
+    exe = native.build("cpp/record_draw")
     W, H = 200, 120
     out = tmp_path / "frame.bin"
     r = subprocess.run([exe, str(out), str(W), str(H)], capture_output=True, text=True, timeout=300)
@@ -63,9 +62,7 @@ def test_cpp_record_draw_with_real_meshes_matches_oracle(tmp_path):
     from oracle import binding as ob
     from syzygy_amd import abi, lib, meshes, scene
 
-    exe = os.path.join(HERE, "cpp", "record_draw")
-    if not os.path.exists(exe):
-        subprocess.run(["make", "-C", os.path.join(HERE, "cpp")], check=True)
+    exe = native.build("cpp/record_draw")
     W, H, DIM = 200, 120, 512
     out = tmp_path / "frame_meshes.bin"
     r = subprocess.run([exe, str(out), str(W), str(H), "meshes"], capture_output=True, text=True, timeout=300)
@@ -108,8 +105,7 @@ def test_cpp_asset_library_gltf_to_frame_matches_oracle(tmp_path):
     from syzygy_amd import abi, assets, lib, meshes, scene
     from tests import gltf_writer as gw
 
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw"], check=True)
-    exe = os.path.join(HERE, "cpp", "record_draw")
+    exe = native.build("cpp/record_draw")
     rng = np.random.default_rng(5)
     pos, nrm, uv, idx = gw.uv_sphere(10, 20)
     b = gw.GltfBuilder()
@@ -179,8 +175,7 @@ def test_cpp_engine_frame_scene_and_renderer_match_oracle(tmp_path):
     from oracle import binding as ob
     from syzygy_amd import abi, assets, lib, meshes, scene
 
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw"], check=True)
-    exe = os.path.join(HERE, "cpp", "record_draw")
+    exe = native.build("cpp/record_draw")
     W, H, DIM, TICKS = 200, 120, 512, 3
     out = tmp_path / "frame_scene.bin"
     r = subprocess.run([exe, str(out), str(W), str(H), "scene", str(TICKS)], capture_output=True, text=True, timeout=300)
@@ -258,8 +253,7 @@ def test_cpp_engine_frame_inside_a_capacity_allocation_equals_the_tight_one(tmp_
     """The engine's configuration (renderer.hpp:93-96, scenetexture.hpp:21-25): Renderer::create and SceneTexture::create at a
     capacity extent, sceneSubregion {0, 0, W, H} inside it. The 70x37 frame drawn into 96x48 images - shadow raster, G-buffer
     raster, lights, sky-view pipeline, read back with the image's pitch - is the file of the tight run byte for byte."""
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw"], check=True)
-    exe = os.path.join(HERE, "cpp", "record_draw")
+    exe = native.build("cpp/record_draw")
     W, H, TICKS = 70, 37, 2
     files = {}
     for name, extra in (("tight", []), ("capacity", ["96", "48"])):
@@ -277,8 +271,7 @@ def test_cpp_tiled_frame_through_the_c_abi_collectives(tmp_path):
     """tests/cpp/record_draw.cpp `tiled`: a C++ caller (no Python, no torch) renders the row-tiled frame as the one rank of a
     world of one - szg_rowtile_comm over RCCL, the sky-view LUT row slice + in-place all-gather, the tile gather to the root,
     the compose kernel - and must produce the plain frame bit for bit."""
-    exe = os.path.join(HERE, "cpp", "record_draw")
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw"], check=True)
+    exe = native.build("cpp/record_draw")
     W, H = 200, 120
     plain, tiled = tmp_path / "plain.bin", tmp_path / "tiled.bin"
     r = subprocess.run([exe, str(plain), str(W), str(H)], capture_output=True, text=True, timeout=300)
@@ -301,9 +294,8 @@ def test_cpp_n_rank_tiled_frame_through_the_c_abi_collectives(tmp_path, ranks, n
     rank then computes the whole LUT and the optional second collective is skipped (pipelines.hpp) - same frame.
     `no_gather` (SZG_RCCL_NO_GATHER): szg_rowtile_gather takes its grouped ncclSend / ncclRecv path - the one a library
     without ncclGather gets - with the root's own tile copied outside the group."""
-    exe = os.path.join(HERE, "cpp", "record_draw")
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "record_draw", "libmock_rccl.so"], check=True)
-    env = dict(os.environ, SZG_RCCL_LIBRARY=os.path.join(HERE, "cpp", "libmock_rccl.so"), SZG_LOG="1")
+    exe = native.build("cpp/record_draw")
+    env = dict(os.environ, SZG_RCCL_LIBRARY=native.build("cpp/libmock_rccl.so"), SZG_LOG="1")
     if no_gather:
         env["SZG_RCCL_NO_GATHER"] = "1"
     W, H = 200, 240
@@ -328,8 +320,7 @@ def test_comm_create_deadline_and_error_paths_of_the_grouped_gather(tmp_path):
     child process: the blocked initialisation cannot be cancelled, only left behind by exiting.
     (b) An error inside the grouped send / recv path closes the group: a gather to a root outside the communicator is refused
     up front, and after a failing call the next, valid, gather on the same communicator still works (world of one)."""
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libmock_rccl.so"], check=True)
-    env = dict(os.environ, SZG_RCCL_LIBRARY=os.path.join(HERE, "cpp", "libmock_rccl.so"), SZG_RCCL_NO_GATHER="1")
+    env = dict(os.environ, SZG_RCCL_LIBRARY=native.build("cpp/libmock_rccl.so"), SZG_RCCL_NO_GATHER="1")
     code = r"""
 import ctypes as C, sys, time
 import torch

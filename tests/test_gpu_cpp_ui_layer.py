@@ -1,19 +1,17 @@
 """The C++ mirror of the UI layer pass (include/szg/ui_layer.hpp: szg::UILayer) through its own interface, from a program built
 with hipcc (tests/cpp/ui_layer_shim.cpp) whose draw data has Dear ImGui's shape: two lists concatenated with global offsets,
 a command with a user callback skipped, the scene viewport quad at the editor's UVs - against the CPU model, bit for bit."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from syzygy_amd import lib
+from tests import native
 from tests import ui_layer_cases as uc
 from tests import ui_layer_model as um
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 def test_uilayer_record_draw_from_cpp(tmp_path):
@@ -22,10 +20,7 @@ def test_uilayer_record_draw_from_cpp(tmp_path):
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    exe = str(tmp_path / "ui_layer_shim")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(HERE, "cpp", "ui_layer_shim.cpp"), "-o", exe, "-L" + csrc, "-lszg_hip", "-Wl,-rpath," + csrc], check=True)
+    exe = native.build("cpp/ui_layer_shim")
     cap, content, display = (64, 48), (37, 29), (53, 41)
     scene = np.random.default_rng(4).integers(0, 65536, (cap[1], cap[0], 4), dtype=np.uint16)
     scene[..., 3] |= 0xC000  # mostly opaque, so that the scene shows

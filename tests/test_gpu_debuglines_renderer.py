@@ -2,7 +2,6 @@
 hipcc (tests/cpp/record_draw_debuglines.cpp). With the switch on, the frame is the switch-off frame with the model's
 lines drawn over it, the list being the one the Python builders make from the same boxes; with it off (before and after),
 the frame is byte-identical and nothing is drawn."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,25 +9,19 @@ import pytest
 
 from syzygy_amd import abi, lib
 from tests import debuglines_model as dm
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
+def exe():
     import torch
 
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    out = str(tmp_path_factory.mktemp("cpp") / "record_draw_debuglines")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(HERE, "cpp", "record_draw_debuglines.cpp"), "-o", out, "-L" + csrc, "-lszg_hip",
-                    "-Wl,-rpath," + csrc], check=True)
-    return out
+    return native.build("cpp/record_draw_debuglines")
 
 
 def python_list(boxes_raw):

@@ -8,18 +8,16 @@ functions on every binary32 input of their documented ranges (the ULP rule of te
 the host build on a stratified sample, and the store formats (UNORM16, fp16) on every input. Each sweep prints what it
 evaluated, its mismatches, its largest error with the operands where it occurs, and its seconds."""
 import ctypes as C
-import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
 from oracle import binding as ob
+from tests import native
 from tests.test_fpmath import check_special_values, ulp_error
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 LAUNCH = 1 << 30  # one launch of the library covers at most this many indices; a sweep loops over launches
 
 PI = float(np.float32(np.pi))
@@ -43,8 +41,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libszg_devarith.so"], check=True)
-        h = C.CDLL(os.path.join(HERE, "cpp", "libszg_devarith.so"))
+        h = C.CDLL(native.build("cpp/libszg_devarith.so"))
         h.szg_da_sweep.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(Params), C.c_double, C.POINTER(Result)]
         h.szg_da_eval.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]
         h.szg_da_unpack_half4.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]

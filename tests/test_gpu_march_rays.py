@@ -10,16 +10,14 @@ make_tlut(t, w, h), and the FramePrep forms behind the product's own k_frame_pre
 Equality rule: every float bit-identical to oracle_scattering_integral of the lane's ray, sign of zero included; NaN for NaN.
 No ray is left out. Hole slots and the slots past n keep the sentinel."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import march_rays as mr
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 class Flags(C.Structure):
@@ -34,8 +32,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "libszg_marchrays.so"], check=True)
-        h = C.CDLL(os.path.join(HERE, "cpp", "libszg_marchrays.so"))
+        h = C.CDLL(native.build("cpp/libszg_marchrays.so"))
         h.szg_mr_run.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_void_p, C.c_uint, C.c_uint32, C.c_void_p,
                                  C.POINTER(Flags)]
         _LIB = h

@@ -2,17 +2,15 @@
 device sampler of syzygy_amd/csrc/szg_texture.hpp in isolation, called by the test-only kernel of tests/mipsample (built by
 its own make rule with the product's HIPFLAGS)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from syzygy_amd import abi, lib
 from tests import mipmap_model as mm
+from tests import native
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
 
 
@@ -89,9 +87,7 @@ def test_refusals_leave_the_output_untouched(gpu):
 # ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mipsample():
-    directory = os.path.join(HERE, "mipsample")
-    subprocess.run(["make", "-s", "-C", directory, "libszg_mipsample.so"], check=True)
-    handle = C.CDLL(os.path.join(directory, "libszg_mipsample.so"))
+    handle = C.CDLL(native.build("mipsample/libszg_mipsample.so"))
     handle.szg_mipsample.restype = C.c_int
     handle.szg_mipsample.argtypes = [C.POINTER(abi.Texture), C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 4 + [C.c_uint32]
     return handle

@@ -13,6 +13,7 @@ import pytest
 
 from syzygy_amd import abi, lib
 from tests import gpu_present_child as child
+from tests import native
 from tests import present_model as pm
 from tests.test_present_model import SCALED_CASES, refusal_cases, region_of
 
@@ -266,14 +267,9 @@ def test_python_wrappers_take_strided_tensors(torch, tables):
 
 
 @pytest.fixture(scope="module")
-def record_present_exe(torch, tmp_path_factory):
+def record_present_exe(torch):
     lib()  # built and loadable
-    out = str(tmp_path_factory.mktemp("cpp") / "record_present")
-    csrc = os.path.join(ROOT, "syzygy_amd", "csrc")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-x", "hip", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(HERE, "cpp", "record_present.cpp"), "-o", out, "-L" + csrc, "-lszg_hip", "-Wl,-rpath," + csrc],
-                   check=True)
-    return out
+    return native.build("cpp/record_present")
 
 
 @pytest.mark.parametrize("fmt", pm.FORMATS)

@@ -6,8 +6,8 @@ import os
 import subprocess
 
 from tests import jpeg_fixtures as jf
+from tests import native
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SEEDS = ["444_17x9_base_q92", "422_33x31_prog_q92", "420_33x31_rst_q92", "420_9x17_prog_q12", "grey_7x5_rst_q12",
          "h1v2_17x17_base_q85", "h4v1_33x16_base_q85", "h1v4_15x31_base_q85", "rgbids_17x9_base_q85", "adobe0_17x9_base_q85",
          "444_130x70_rst_q12", "refused_cmyk_17x9"]
@@ -15,9 +15,9 @@ MUTANTS = 1500
 
 
 def test_jpeg_host_code_survives_corrupted_input_under_sanitizers():
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "jpeg"), "fuzz_jpeg"], check=True)
+    exe = native.build("jpeg/fuzz_jpeg")
     files = [os.path.join(jf.FOLDER, name + ".jpg") for name in SEEDS]
-    out = subprocess.run([os.path.join(HERE, "jpeg", "fuzz_jpeg"), str(MUTANTS)] + files, capture_output=True, text=True, timeout=600,
+    out = subprocess.run([exe, str(MUTANTS)] + files, capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:allocator_may_return_null=1:max_allocation_size_mb=4096"))
     assert out.returncode == 0, out.stderr[-4000:]
     lines = out.stdout.splitlines()
