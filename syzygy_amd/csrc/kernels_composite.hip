@@ -412,15 +412,19 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     asm volatile("" ::: "memory");
     // The frame's constants move from the scalar block to vector registers again (load_atm: ~45 moves per wave), so that
     // phase A's copies die with phase A instead of being spilled around the march.
-    Atm const aB = load_atm(*prep);
-#ifdef SZG_EXP_LDS_TLUT
-    TLut const& LB = L;
-#else
-    TLut const LB = make_tlut(tlut, tW, tH, *prep);
-#endif
 #pragma unroll 1
     for (unsigned k = 0; k < 2u; k++)
     {
+        // ... and once per slot, behind a fence that keeps the loads from being hoisted out of the loop: constants that only
+        // the per-ray set-up reads would otherwise stay live across slot 0's march for slot 1's set-up, in scratch. The loads
+        // are scalar and do not depend on which slots the wave runs.
+        asm volatile("" ::: "memory");
+        Atm const aB = load_atm(*prep);
+#ifdef SZG_EXP_LDS_TLUT
+        TLut const& LB = L;
+#else
+        TLut const LB = make_tlut(tlut, tW, tH, *prep);
+#endif
         if (((s_flags[tid] >> k) & 1u) != 0u)
         {
             V3 const o = mk3(s_request[k][0][tid], s_request[k][1][tid], s_request[k][2][tid]);
@@ -433,16 +437,22 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     }
     asm volatile("" ::: "memory");
 
-    unsigned const flags = s_flags[tid];
+    // Phase C addresses its pixel and its LDS slots from the thread index again, through a copy the compiler cannot see
+    // through: x, y and the slot addresses of phase A would otherwise wait for it in scratch across the march.
+    unsigned tidC = tid;
+    asm volatile("" : "+v"(tidC));
+    unsigned const xC = blockIdx.x * 32u + (tidC >> 6) * 8u + (tidC & 7u);
+    unsigned const yC = (gridDim.y - 1u - blockIdx.y) * 8u + ((tidC & 63u) >> 3);
+    unsigned const flags = s_flags[tidC];
     march0 = (flags & 1u) != 0u;
     march1 = (flags & 2u) != 0u;
     hasReflection = (flags & 4u) != 0u;
-    V3 const ap0 = march0 ? mk3(s_result[0][0][tid], s_result[0][1][tid], s_result[0][2][tid]) : splat(0.0f);
-    V3 const ap1 = march1 ? mk3(s_result[1][0][tid], s_result[1][1][tid], s_result[1][2][tid]) : splat(0.0f);
-    base = mk3(s_park[0][tid], s_park[1][tid], s_park[2][tid]);
-    coef = mk3(s_park[3][tid], s_park[4][tid], s_park[5][tid]);
-    env2 = mk3(s_park[6][tid], s_park[7][tid], s_park[8][tid]);
-    surfaceLuminance = mk3(s_park[9][tid], s_park[10][tid], s_park[11][tid]);
+    V3 const ap0 = march0 ? mk3(s_result[0][0][tidC], s_result[0][1][tidC], s_result[0][2][tidC]) : splat(0.0f);
+    V3 const ap1 = march1 ? mk3(s_result[1][0][tidC], s_result[1][1][tidC], s_result[1][2][tidC]) : splat(0.0f);
+    base = mk3(s_park[0][tidC], s_park[1][tidC], s_park[2][tidC]);
+    coef = mk3(s_park[3][tidC], s_park[4][tidC], s_park[5][tidC]);
+    env2 = mk3(s_park[6][tidC], s_park[7][tidC], s_park[8][tidC]);
+    surfaceLuminance = mk3(s_park[9][tidC], s_park[10][tidC], s_park[11][tidC]);
     // ---- phase C ---------------------------------------------------------
     // sky:      transfer = env(position, direction)
     // geometry: transfer = (surfaceTransfer + AP) + coef * env(reflection)
@@ -456,10 +466,10 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     V3 const luminance = transfer * mk3(prep->a.sunIntensitySpectrum.x, prep->a.sunIntensitySpectrum.y, prep->a.sunIntensitySpectrum.z);
     V3 const pre = luminance * 10.0f + surfaceLuminance;
     V3 const out = mk3(szg_powf(pre.x, 1.2f), szg_powf(pre.y, 1.2f), szg_powf(pre.z, 1.2f));
-    row_ptr<uint2>(color, y)[x] = pack_unorm16x4(out.x, out.y, out.z, 1.0f);
+    row_ptr<uint2>(color, yC)[xC] = pack_unorm16x4(out.x, out.y, out.z, 1.0f);
     if (debug.data != nullptr)
     {
-        row_ptr<float4>(debug, y)[x] = make_float4(out.x, out.y, out.z, 1.0f);
+        row_ptr<float4>(debug, yC)[xC] = make_float4(out.x, out.y, out.z, 1.0f);
     }
 }
 

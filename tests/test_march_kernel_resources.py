@@ -1,0 +1,53 @@
+"""What the compiler reports for the kernels that hold the march (`make march-resource-usage` in syzygy_amd/csrc: the library's
+flags and per-unit scheduler options, -Rpass-analysis=kernel-resource-usage). k_composite runs four waves per SIMD without
+scratch and with an LDS queue small enough for four workgroups per CU (4 x 40 960 B = 160 KiB); k_skyview likewise without
+scratch. Only the remark lines are read."""
+import os
+import re
+import subprocess
+
+import pytest
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "syzygy_amd", "csrc")
+FIELDS = {"VGPRs": r"\bVGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)", "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)",
+          "lds": r"LDS Size \[bytes/block\]: (\d+)"}
+
+
+@pytest.fixture(scope="module")
+def remarks():
+    done = subprocess.run(["make", "-C", CSRC, "march-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert done.returncode == 0, done.stdout[-4000:]
+    kernels, current = {}, None
+    for line in done.stdout.splitlines():
+        if "remark:" not in line:
+            continue
+        name = re.search(r"Function Name: (\S+)", line)
+        if name:
+            current = kernels.setdefault(name.group(1), {})
+            continue
+        for field, pattern in FIELDS.items():
+            m = re.search(pattern, line)
+            if m and current is not None:
+                current[field] = int(m.group(1))
+    return kernels
+
+
+def one(remarks, fragment):
+    found = [(n, r) for n, r in remarks.items() if fragment in n]
+    assert len(found) == 1, (fragment, [n for n, _ in found])
+    assert set(found[0][1]) == set(FIELDS), found[0]
+    return found[0][1]
+
+
+# (Itanium mangling: k_composite<true> is ...k_compositeILb1EEE..., k_composite<false> ...ILb0EEE...)
+@pytest.mark.parametrize("fragment", ["11k_compositeILb0EE", "11k_compositeILb1EE"])
+def test_composite_has_no_scratch_at_four_waves(remarks, fragment):
+    r = one(remarks, fragment)
+    print(fragment, r)
+    assert r["scratch"] == 0 and r["VGPRs"] <= 128 and r["occupancy"] == 4 and r["lds"] <= 40960, r
+
+
+def test_skyview_has_no_scratch_at_four_waves(remarks):
+    r = one(remarks, "9k_skyviewE")
+    print(r)
+    assert r["scratch"] == 0 and r["occupancy"] == 4, r
