@@ -12,11 +12,12 @@
     --pipeline compute-collection[:NAME]: the editor's other        renderer.cpp:431-438 (szg/compute_collection.h)
       rendering pipeline instead of the deferred one
     --ui-layer: the UI draw between the scene and the OETF          editor.cpp:720-748, uilayer.cpp:513-572 (szg/ui_layer.h)
+    --texture-viewer: the Texture Viewer window in that UI          editor.cpp:485-505, :684-692 (szg/texture_display.h)
 
     python examples/frame_loop.py --frames 60 --width 1920 --height 1080 --out /tmp/frame.ppm [--debug-lines [--line-width 2]]
                                   [--present 1280x720[:rgba8|bgra8|a2b10g10r10]]
                                   [--pipeline compute-collection[:booleanpush|gradient_color|sparse_push_constant|matrix_color]]
-                                  [--ui-layer]
+                                  [--ui-layer [--texture-viewer[=color|normal|orm|gbuffer-normal]]]
 
 --pipeline mirrors the editor's "Deferred" / "Compute Collection" switch (ui/engineui.cpp:19-22). With compute-collection
 the frame uploads and fills the debug-line list as before, then records ONE program of the collection over the scene colour
@@ -27,6 +28,10 @@ or debug-line launches. The OETF and --present follow as in the editor.
 viewport window, a draw list made with syzygy_amd.ui (a title bar, the scene viewport quad at the editor's UVs, a translucent
 side panel, a frame-time graph of filled rectangles) is drawn by UILayer::recordDraw into the output texture, and the OETF,
 --present and --out work on that OUTPUT image, as Editor::endFrame does.
+
+--texture-viewer (with --ui-layer) adds a "Texture Viewer" panel: a small RGBA16_SFLOAT display image (the editor's is 4096^2),
+into which every frame the picked texture is blitted (pipelines.TextureDisplay.select: a material map of the scene, or the
+G-buffer's normal plane after the frame's raster pass) and which ui.DrawList.add_image draws in the side panel.
 
 Without --present the 16-bit scene colour is copied to the host and the PPM holds its high bytes; with it every frame ends
 with the reference's LINEAR blit onto a WxH image of the given swapchain format (default rgba8) and the PPM is that image
@@ -65,7 +70,11 @@ def main(argv=None):
                          "(default), reference (the reference sampler's 1.0) or a number")
     ap.add_argument("--ui-layer", action="store_true",
                     help="draw an editor-like UI frame over the scene (szg/ui_layer.h) and present the UI output texture")
+    ap.add_argument("--texture-viewer", nargs="?", const="color", default=None, choices=["color", "normal", "orm", "gbuffer-normal"],
+                    help="with --ui-layer: a Texture Viewer panel showing a material map or the G-buffer's normal plane (szg/texture_display.h)")
     args = ap.parse_args(argv)
+    if args.texture_viewer and not args.ui_layer:
+        ap.error("--texture-viewer needs --ui-layer")
 
     import torch
 
@@ -124,6 +133,12 @@ def main(argv=None):
         view_min = (panel_w + 6, title_h + 6)
         ui_layer.setSceneViewportExtent(W - view_min[0] - 6, H - view_min[1] - 6)  # the "Scene Viewport" window's content
         frame_times = []
+        viewer = None
+        if args.texture_viewer:  # editor.cpp:485-505, with a small display image instead of TEXTURE_MAX^2
+            viewer = pl.TextureDisplay(ui_layer, (256, 256))
+            if args.texture_viewer != "gbuffer-normal":
+                texels, viewer_srgb = material[args.texture_viewer]
+                viewer_map = torch.from_numpy(np.ascontiguousarray(texels)).cuda()
     target = ui_layer.sceneTexture() if ui_layer else pl.SceneTexture(W, H)
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=len(spots), max_shadow_maps=2 + len(spots), shadow_map_dim=args.shadow_map)
     sky = pl.SkyViewComputePipeline.create()
@@ -189,6 +204,15 @@ def main(argv=None):
             for i, ms in enumerate(frame_times):  # frame-time graph
                 x = 8 + i * bar_w
                 dl.add_rect_filled((x, H - 12 - 4.0 * ms), (x + bar_w * 0.8, H - 12), ui.col32(230, 180, 60, 200))
+            if viewer:  # editor.cpp:684-692 -> texturedisplay.cpp:164-195, :291-304
+                if args.texture_viewer == "gbuffer-normal":
+                    viewer.select(None, deferred.gbuffer().normal, srcRegion=rect)
+                else:
+                    viewer.select(None, viewer_map, srgb=viewer_srgb)
+                side = float(panel_w - 16)
+                size = viewer.imageSize(side)
+                dl.add_rect_filled((6, title_h + 6), (10 + side, title_h + 10 + size[1]), ui.col32(41, 74, 122, 255))
+                dl.add_image(viewer.handle, (8, title_h + 8), (8 + size[0], title_h + 8 + size[1]))
             dl.pop_clip_rect()
             presented = ui_layer.recordDraw(None, ui.DrawData((0, 0), (W, H), (1, 1), [dl])).texture
         pl.recordOETF(None, presented, W, H)
@@ -211,6 +235,8 @@ def main(argv=None):
     if args.debug_lines:
         print(f"debug lines: {debug_lines.lastFrameDrawResults.verticesDrawn // 2} lines, width {debug_lines.lineWidth}")
     if ui_layer:
+        if viewer:
+            viewer.cleanup()
         ui_layer.cleanup()
     debug_lines.cleanup()
     deferred.cleanup()

@@ -181,7 +181,9 @@ typedef enum szg_format
     /* destinations of the present pass only (szg/present.h; the swapchain formats of editor/swapchain.cpp:99-103) */
     SZG_FORMAT_RGBA8_UNORM = 5,        /* 4 B/texel : bytes R, G, B, A */
     SZG_FORMAT_BGRA8_UNORM = 6,        /* 4 B/texel : bytes B, G, R, A */
-    SZG_FORMAT_A2B10G10R10_UNORM = 7   /* 4 B/texel : one little-endian dword, R bits 0-9, G 10-19, B 20-29, A 30-31 */
+    SZG_FORMAT_A2B10G10R10_UNORM = 7,  /* 4 B/texel : one little-endian dword, R bits 0-9, G 10-19, B 20-29, A 30-31 */
+    /* a source of the image copy only (szg/texture_display.h; the colour maps of assets.cpp:706-715) */
+    SZG_FORMAT_RGBA8_SRGB = SZG_FORMAT_A2B10G10R10_UNORM + 1 /* 8. 4 B/texel : bytes R, G, B, A; R, G, B sRGB-encoded */
 } szg_format;
 
 /* An image may be allocated larger than what a pass draws, as the reference's are (scene texture and G-buffer at a capacity

@@ -17,6 +17,8 @@
 //   Editor::endFrame's tail     editor.cpp:303-361         szg::recordPresent
 //   ComputeCollectionPipeline   pipelines.hpp:166-235      szg::ComputeCollectionPipeline (szg/compute_collection.h)
 //   UILayer                     editor/uilayer.hpp:36-114  szg::UILayer (szg/ui_layer.hpp, included at the end; szg/ui_layer.h)
+//   TextureDisplay              ui/texturedisplay.hpp      szg::TextureDisplay (szg/texture_display.hpp, included at the end;
+//                                                          szg/texture_display.h)
 //   std::span<MeshInstanced const> sceneGeometry           szg_fill_scene const* (synthetic)
 //
 // Error behaviour follows the reference: construction failures give an invalid object /
@@ -39,6 +41,7 @@
 #include "szg/mipmaps.h"
 #include "szg/present.h"
 #include "szg/raster.h"
+#include "szg/texture_display.h"
 #include "szg/host.h"
 
 namespace szg
@@ -511,7 +514,8 @@ inline auto recordCopyImageToImage(hipStream_t cmd, szg_image const& source, szg
 }
 // imageoperations.cpp:141-176: the form behind Image::recordCopyEntire / recordCopyRect (image.cpp:185-229), corners instead
 // of rectangles and VK_FILTER_NEAREST (:169). The aspect mask is dropped (colour only); a max corner below its min corner (a
-// flipped blit, which a szg_rect cannot express) is refused.
+// flipped blit, which a szg_rect cannot express) is refused. An RGBA16_SFLOAT destination (the texture viewer's display image,
+// the reference's own use of this form) is the image copy of szg/texture_display.h; every other one the present pass, as ever.
 struct Offset2D
 {
     int32_t x, y;
@@ -528,6 +532,11 @@ inline auto recordCopyImageToImage(hipStream_t cmd, szg_image const& src, szg_im
         szg_rect{srcMin.x, srcMin.y, static_cast<uint32_t>(srcMax.x - srcMin.x), static_cast<uint32_t>(srcMax.y - srcMin.y)},
         szg_rect{dstMin.x, dstMin.y, static_cast<uint32_t>(dstMax.x - dstMin.x), static_cast<uint32_t>(dstMax.y - dstMin.y)},
         SZG_FILTER_NEAREST, SZG_PRESENT_ENCODE_NONE};
+    if (dst.format == SZG_FORMAT_RGBA16_SFLOAT)
+    {
+        return detail::note(szg_record_copy_image(cmd, &src, &dst, info.src_region, info.dst_region), "szg_record_copy_image",
+                            detail::presentStatus());
+    }
     return detail::note(szg_record_present(cmd, &src, &dst, &info), "szg_record_present", detail::presentStatus());
 }
 
@@ -660,3 +669,5 @@ struct ComputeCollectionPipeline
 
 // UILayer (editor/uilayer.hpp): builds on SceneTexture, TStagedBuffer and detail::note above
 #include "szg/ui_layer.hpp"
+// TextureDisplay (ui/texturedisplay.hpp): builds on UILayer and recordCopyImageToImage above
+#include "szg/texture_display.hpp"

@@ -6,7 +6,9 @@
 //   UILayer::create(..., VkExtent2D textureCapacity, ...)       szg::UILayer::create(textureCapacity): both textures at the
 //     uilayer.cpp:285-328                                         capacity, the scene texture registered NEAREST / CLAMP_TO_BORDER
 //   ImGui_ImplVulkan_Init / CreateDeviceObjects                 (inside create: szg_ui_layer_create)
-//   ImGui_ImplVulkan_AddTexture(sampler, view, layout)          addTexture(image, sampler) -> szg_ui_texture_t*, usable as ImTextureID
+//   ImGui_ImplVulkan_AddTexture(sampler, view, layout)          addTexture(image, sampler) -> szg_ui_texture_t*, usable as ImTextureID;
+//                                                                 addTextureView(image, sampler, view) for a view with a component
+//                                                                 mapping or a half-float image (szg/texture_display.h)
 //   UILayer::sceneTexture(), sceneViewport(forceFocus)          the same names; {focused, texture, renderedSubregion}
 //   UILayer::recordDraw(cmd) -> optional<UIOutputImage>         recordDraw(cmd, drawData): ImGui::GetDrawData() is the caller's
 //     uilayer.cpp:513-572
@@ -29,6 +31,7 @@
 #include <utility>
 
 #include "szg/pipelines.hpp"
+#include "szg/texture_display.h"
 #include "szg/ui_layer.h"
 
 namespace szg
@@ -128,6 +131,13 @@ struct UILayer
     {
         szg_ui_texture_t* out = nullptr;
         detail::note(szg_ui_layer_add_texture(m_layer, &image, sampler, &out), "szg_ui_layer_add_texture", m_lastStatus);
+        return out;
+    }
+    // the same with an image view (szg/texture_display.h): RGBA16_SFLOAT images too, `view` maps the components
+    auto addTextureView(szg_image const& image, szg_ui_sampler sampler, szg_ui_texture_view const& view) -> szg_ui_texture_t*
+    {
+        szg_ui_texture_t* out = nullptr;
+        detail::note(szg_ui_layer_add_texture_view(m_layer, &image, sampler, &view, &out), "szg_ui_layer_add_texture_view", m_lastStatus);
         return out;
     }
     void removeTexture(szg_ui_texture_t* texture)

@@ -33,8 +33,11 @@ SZG_FORMAT_D32_SFLOAT = 4
 SZG_FORMAT_RGBA8_UNORM = 5
 SZG_FORMAT_BGRA8_UNORM = 6
 SZG_FORMAT_A2B10G10R10_UNORM = 7
+# a source of the image copy (include/szg/texture_display.h)
+SZG_FORMAT_RGBA8_SRGB = 8
 
 TEXEL_BYTES = {
+    SZG_FORMAT_RGBA8_SRGB: 4,
     SZG_FORMAT_RGBA16_SFLOAT: 8,
     SZG_FORMAT_RGBA32_SFLOAT: 16,
     SZG_FORMAT_RGBA16_UNORM: 8,
@@ -646,6 +649,27 @@ UI_LAYER_FUNCTIONS = {
     "szg_ui_layer_add_texture": (C.c_int, [VP, P(Image), UISampler, P(VP)]),
     "szg_ui_layer_remove_texture": (C.c_int, [VP, VP]),
     "szg_ui_layer_record_draw": (C.c_int, [VP, VP, P(Image), Rect, U32, P(C.c_float), P(UIDrawData)]),
+}
+
+# include/szg/texture_display.h
+SZG_SWIZZLE_IDENTITY = 0
+SZG_SWIZZLE_ZERO = 1
+SZG_SWIZZLE_ONE = 2
+SZG_SWIZZLE_R = 3
+SZG_SWIZZLE_G = 4
+SZG_SWIZZLE_B = 5
+SZG_SWIZZLE_A = 6
+
+
+class UITextureView(C.Structure):
+    """VkComponentMapping: swizzle[0..3] produce R, G, B, A"""
+    _fields_ = [("swizzle", U32 * 4)]
+
+
+TEXTURE_DISPLAY_FUNCTIONS = {
+    "szg_record_copy_image": (C.c_int, [VP, P(Image), P(Image), Rect, Rect]),
+    "szg_record_clear_color_image": (C.c_int, [VP, P(Image), P(C.c_float)]),
+    "szg_ui_layer_add_texture_view": (C.c_int, [VP, P(Image), UISampler, P(UITextureView), P(VP)]),
 }
 
 

@@ -57,6 +57,7 @@ unsigned texel_bytes(unsigned fmt)
     case SZG_FORMAT_RGBA8_UNORM:
     case SZG_FORMAT_BGRA8_UNORM:
     case SZG_FORMAT_A2B10G10R10_UNORM:
+    case SZG_FORMAT_RGBA8_SRGB:
         return 4;
     default:
         return 0;

@@ -15,6 +15,7 @@ struct szg_ui_texture
 {
     szg_image image{};
     szg_ui_sampler sampler{};
+    uint32_t swizzle[4] = {}; // szg_ui_texture_view (szg/texture_display.h); all IDENTITY from szg_ui_layer_add_texture
 };
 
 struct szg_ui_layer
@@ -38,9 +39,10 @@ void image_bytes(const szg_image& im, uintptr_t& begin, uintptr_t& end)
     end = begin + (im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format));
 }
 
-// present, of an accepted format (the output: RGBA16_UNORM; a texture: that or RGBA8_UNORM), not above the extent cap, rows
-// inside the pitch, texels naturally aligned
-bool check_ui_image(const char* caller, const szg_image* im, bool isOutput, const char* name)
+// present, of an accepted format (the output: RGBA16_UNORM; a texture: that or RGBA8_UNORM, and with `allowHalf`, the
+// textures of szg_ui_layer_add_texture_view, RGBA16_SFLOAT), not above the extent cap, rows inside the pitch, texels naturally
+// aligned
+bool check_ui_image(const char* caller, const szg_image* im, bool isOutput, const char* name, bool allowHalf = false)
 {
     if (im == nullptr || im->data == nullptr)
     {
@@ -48,10 +50,14 @@ bool check_ui_image(const char* caller, const szg_image* im, bool isOutput, cons
         return false;
     }
     bool const formatOk = isOutput ? im->format == SZG_FORMAT_RGBA16_UNORM
-                                   : (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_RGBA16_UNORM);
+                                   : (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_RGBA16_UNORM ||
+                                      (allowHalf && im->format == SZG_FORMAT_RGBA16_SFLOAT));
     if (!formatOk)
     {
-        fail(SZG_ERR_INVALID_ARGUMENT, isOutput ? "%s: %s format %u, must be RGBA16_UNORM" : "%s: %s format %u, must be RGBA8_UNORM or RGBA16_UNORM",
+        fail(SZG_ERR_INVALID_ARGUMENT,
+             isOutput    ? "%s: %s format %u, must be RGBA16_UNORM"
+             : allowHalf ? "%s: %s format %u, must be RGBA8_UNORM, RGBA16_UNORM or RGBA16_SFLOAT"
+                         : "%s: %s format %u, must be RGBA8_UNORM or RGBA16_UNORM",
              caller, name, im->format);
         return false;
     }
@@ -95,6 +101,51 @@ int trunc_saturated(float x)
         return INT32_MIN;
     }
     return (int)x;
+}
+
+// ImGui_ImplVulkan_AddTexture behind both registrations: `view` NULL is the identity mapping, `allowHalf` admits RGBA16_SFLOAT
+int add_texture(const char* me, szg_ui_layer* layer, const szg_image* image, szg_ui_sampler sampler, const szg_ui_texture_view* view,
+                bool allowHalf, szg_ui_texture_t** out)
+{
+    if (layer == nullptr || out == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: NULL argument", me);
+    }
+    *out = nullptr;
+    if (!check_ui_image(me, image, false, "texture", allowHalf))
+    {
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
+    if (sampler.filter != SZG_FILTER_NEAREST && sampler.filter != SZG_FILTER_LINEAR)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: unknown filter %u", me, sampler.filter);
+    }
+    if (sampler.address != SZG_UI_ADDRESS_REPEAT && sampler.address != SZG_UI_ADDRESS_CLAMP_TO_EDGE &&
+        sampler.address != SZG_UI_ADDRESS_CLAMP_TO_BORDER)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: unknown address mode %u", me, sampler.address);
+    }
+    for (int i = 0; view != nullptr && i < 4; i++)
+    {
+        if (view->swizzle[i] > SZG_SWIZZLE_A)
+        {
+            return fail(SZG_ERR_INVALID_ARGUMENT, "%s: swizzle[%d] = %u is no component swizzle", me, i, view->swizzle[i]);
+        }
+    }
+    std::unique_ptr<szg_ui_texture> t(new (std::nothrow) szg_ui_texture());
+    if (!t)
+    {
+        return fail(SZG_ERR_OUT_OF_MEMORY, "%s: host allocation failed", me);
+    }
+    t->image = *image;
+    t->sampler = sampler;
+    for (int i = 0; view != nullptr && i < 4; i++)
+    {
+        t->swizzle[i] = view->swizzle[i];
+    }
+    *out = t.get();
+    layer->textures.push_back(std::move(t));
+    return SZG_OK;
 }
 } // namespace
 
@@ -164,34 +215,14 @@ void szg_ui_layer_destroy(szg_ui_layer_t* layer)
 
 int szg_ui_layer_add_texture(szg_ui_layer_t* layer, const szg_image* image, szg_ui_sampler sampler, szg_ui_texture_t** out)
 {
-    if (layer == nullptr || out == nullptr)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_ui_layer_add_texture: NULL argument");
-    }
-    *out = nullptr;
-    if (!check_ui_image("szg_ui_layer_add_texture", image, false, "texture"))
-    {
-        return SZG_ERR_INVALID_ARGUMENT;
-    }
-    if (sampler.filter != SZG_FILTER_NEAREST && sampler.filter != SZG_FILTER_LINEAR)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_ui_layer_add_texture: unknown filter %u", sampler.filter);
-    }
-    if (sampler.address != SZG_UI_ADDRESS_REPEAT && sampler.address != SZG_UI_ADDRESS_CLAMP_TO_EDGE &&
-        sampler.address != SZG_UI_ADDRESS_CLAMP_TO_BORDER)
-    {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_ui_layer_add_texture: unknown address mode %u", sampler.address);
-    }
-    std::unique_ptr<szg_ui_texture> t(new (std::nothrow) szg_ui_texture());
-    if (!t)
-    {
-        return fail(SZG_ERR_OUT_OF_MEMORY, "szg_ui_layer_add_texture: host allocation failed");
-    }
-    t->image = *image;
-    t->sampler = sampler;
-    *out = t.get();
-    layer->textures.push_back(std::move(t));
-    return SZG_OK;
+    return add_texture("szg_ui_layer_add_texture", layer, image, sampler, nullptr, false, out);
+}
+
+// include/szg/texture_display.h: the same registration with an image view, and RGBA16_SFLOAT among the formats
+int szg_ui_layer_add_texture_view(szg_ui_layer_t* layer, const szg_image* image, szg_ui_sampler sampler, const szg_ui_texture_view* view,
+                                  szg_ui_texture_t** out)
+{
+    return add_texture("szg_ui_layer_add_texture_view", layer, image, sampler, view, true, out);
 }
 
 int szg_ui_layer_remove_texture(szg_ui_layer_t* layer, szg_ui_texture_t* texture)
@@ -347,7 +378,13 @@ int szg_ui_layer_record_draw(szg_ui_layer_t* layer, void* stream, const szg_imag
         c.texWidth = tex->image.width;
         c.texHeight = tex->image.height;
         c.texPitch = tex->image.pitch_bytes;
-        c.tex16 = tex->image.format == SZG_FORMAT_RGBA16_UNORM ? 1u : 0u;
+        c.texFormat = tex->image.format == SZG_FORMAT_RGBA16_UNORM    ? UI_TEX_RGBA16_UNORM
+                      : tex->image.format == SZG_FORMAT_RGBA16_SFLOAT ? UI_TEX_RGBA16_SFLOAT
+                                                                      : UI_TEX_RGBA8_UNORM;
+        for (unsigned k = 0; k < 4u; k++)
+        {
+            c.texFormat |= tex->swizzle[k] << (16u + 3u * k);
+        }
         c.filter = tex->sampler.filter;
         c.address = tex->sampler.address;
         for (int k = 0; k < 4; k++)

@@ -22,6 +22,7 @@
 #include "szg_device.hpp"
 #include "szg_launch.hpp"
 
+#include "szg/texture_display.h"
 #include "szg/ui_layer.h"
 
 namespace szg
@@ -224,9 +225,14 @@ SZG_DEV V4 fetchTexel(const UICommand& c, int i, int j, bool outside)
         return V4{0.0f, 0.0f, 0.0f, 1.0f};
     }
     const unsigned char* row = static_cast<const unsigned char*>(c.texData) + (size_t)j * c.texPitch;
-    if (c.tex16 != 0u)
+    unsigned const format = c.texFormat & 0xFFFFu; // per command: wave-uniform
+    if (format != UI_TEX_RGBA8_UNORM)
     {
         uint2 const t = *reinterpret_cast<const uint2*>(row + (size_t)i * 8u);
+        if (format == UI_TEX_RGBA16_SFLOAT)
+        {
+            return unpack_half4(t); // exact: denormals kept, inf and NaN as they are
+        }
         return V4{unorm16ToFloat(t.x & 0xFFFFu), unorm16ToFloat(t.x >> 16), unorm16ToFloat(t.y & 0xFFFFu), unorm16ToFloat(t.y >> 16)};
     }
     unsigned const t = *reinterpret_cast<const unsigned*>(row + (size_t)i * 4u);
@@ -234,7 +240,36 @@ SZG_DEV V4 fetchTexel(const UICommand& c, int i, int j, bool outside)
               (float)(t >> 24) / 255.0f};
 }
 
+// MAPPING of szg/texture_display.h for one channel of the filtered sample: `s` is a VkComponentSwizzle, `own` the channel's
+// own value (IDENTITY)
+SZG_DEV float swizzled(V4 r, unsigned s, float own)
+{
+    return s == SZG_SWIZZLE_IDENTITY ? own
+         : s == SZG_SWIZZLE_ZERO     ? 0.0f
+         : s == SZG_SWIZZLE_ONE      ? 1.0f
+         : s == SZG_SWIZZLE_R        ? r.x
+         : s == SZG_SWIZZLE_G        ? r.y
+         : s == SZG_SWIZZLE_B        ? r.z
+                                     : r.w;
+}
+
+SZG_DEV V4 filteredSample(const UICommand& c, float u, float v);
+
+// SAMPLING, then MAPPING. The mapping is per command, hence wave-uniform: a scalar branch that an identity view (every
+// szg_ui_layer_add_texture handle) skips.
 SZG_DEV V4 sampleUI(const UICommand& c, float u, float v)
+{
+    V4 const r = filteredSample(c, u, v);
+    unsigned const map = c.texFormat >> 16;
+    if (map == 0u)
+    {
+        return r;
+    }
+    return V4{swizzled(r, map & 7u, r.x), swizzled(r, (map >> 3) & 7u, r.y), swizzled(r, (map >> 6) & 7u, r.z),
+              swizzled(r, (map >> 9) & 7u, r.w)};
+}
+
+SZG_DEV V4 filteredSample(const UICommand& c, float u, float v)
 {
     AxisTaps const tx = axisTaps(u, c.texWidth, c.filter, c.address);
     AxisTaps const ty = axisTaps(v, c.texHeight, c.filter, c.address);

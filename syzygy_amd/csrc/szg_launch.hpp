@@ -9,6 +9,7 @@
 #include "szg/debuglines.h"
 #include "szg/present.h"
 #include "szg/raster.h"
+#include "szg/texture_display.h"
 #include "szg/ui_layer.h"
 
 namespace szg
@@ -235,6 +236,13 @@ hipError_t launch_debug_lines(hipStream_t s, const szg_scene_texture& scene, uns
 hipError_t launch_present(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_present_info& info,
                           const unsigned short* table);
 
+// ---- image copy and clear of the texture viewer (kernels_image_copy.hip, include/szg/texture_display.h) ----
+// rows a lane of k_image_copy / k_image_clear walks with the column setup it made once
+constexpr unsigned IMAGE_COPY_ROWS_PER_LANE = 8u;
+// Arguments already validated (api_texture_display.cpp); regions without texels launch nothing.
+hipError_t launch_image_copy(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_rect& srcRegion, const szg_rect& dstRegion);
+hipError_t launch_image_clear(hipStream_t s, const szg_image& image, const float color[4]);
+
 // ---- UI layer pass (kernels_ui_layer.hip, include/szg/ui_layer.h) ----
 // One ImDrawCmd that can draw, as the host resolved it (api_ui_layer.cpp): the texture and sampler its handle names, the
 // pixel box scissor ∩ viewport ∩ render area ∩ image, and its triangles after ASSEMBLY's truncation. Read through scalar loads.
@@ -242,13 +250,16 @@ struct UICommand
 {
     const void* texData;
     unsigned texWidth, texHeight, texPitch;
-    unsigned tex16;  // 0: RGBA8_UNORM, 1: RGBA16_UNORM
+    // low half: UI_TEX_RGBA8_UNORM / UI_TEX_RGBA16_UNORM / UI_TEX_RGBA16_SFLOAT; high half: the view's four 3-bit swizzles
+    // (szg/texture_display.h MAPPING), slot i at bit 16 + 3 i. A szg_ui_layer_add_texture handle gives 0 or 1, as ever.
+    unsigned texFormat;
     unsigned filter, address;
     int clip[4];     // x0, y0, x1, y1 (exclusive)
     unsigned vtxOffset, firstIndex, triCount;
     unsigned firstTri; // submission-order number of the command's first triangle
 };
 static_assert(sizeof(UICommand) == 64, "UICommand layout");
+constexpr unsigned UI_TEX_RGBA8_UNORM = 0u, UI_TEX_RGBA16_UNORM = 1u, UI_TEX_RGBA16_SFLOAT = 2u;
 // One triangle after setup, sign-normalised (everything multiplied by s = sign(det)): the edge functions at the centre of
 // pixel (0, 0) and their steps per pixel, exact; which edges are left or top; the attributes, vertex i opposite edge i.
 struct UIPrim

@@ -11,6 +11,8 @@ Names, argument order and meaning follow the reference:
   record_copy_image_to_image / record_present   renderer/imageoperations.cpp:45-176, editor/editor.cpp:303-361
   ComputeCollectionPipeline renderer/pipelines.hpp:166-235, pipelines.cpp:223-368
   UILayer                   editor/uilayer.hpp:36-114, uilayer.cpp:285-337, :412-450, :513-572 (the draw only: szg/ui_layer.h)
+  TextureDisplay, record_copy_image, record_clear_color_image   ui/texturedisplay.cpp, renderer/image.cpp:185-229,
+                            rendercommands.cpp:25 (szg/texture_display.h)
 with `cmd` (VkCommandBuffer) replaced by a HIP stream handle and Vulkan images by
 linear device buffers. torch is used only to own device memory and streams.
 """
@@ -396,9 +398,60 @@ def record_present(cmd, sceneTexture, sourceSubregion, swapchainImage, gammaFunc
 
 
 # ---------------------------------------------------------------------------
+# Image copy and clear of the texture viewer (include/szg/texture_display.h)
+# ---------------------------------------------------------------------------
+_UINT16 = getattr(torch, "uint16", torch.int16)
+
+
+def _tensor_format(tensor, fmt=None, srgb=False):
+    """The szg_format of an [h, w, 4] tensor: uint8 is RGBA8_UNORM (RGBA8_SRGB with `srgb`), int16 / uint16 RGBA16_UNORM,
+    float16 RGBA16_SFLOAT; `fmt` names it explicitly and must fit the element size."""
+    if tensor.dtype == torch.uint8:
+        natural = abi.SZG_FORMAT_RGBA8_SRGB if srgb else abi.SZG_FORMAT_RGBA8_UNORM
+    elif tensor.dtype in (torch.int16, _UINT16):
+        natural = abi.SZG_FORMAT_RGBA16_UNORM
+    elif tensor.dtype == torch.float16:
+        natural = abi.SZG_FORMAT_RGBA16_SFLOAT
+    else:
+        raise ValueError(f"an image holds uint8, 16-bit codes or float16, got {tensor.dtype}")
+    if fmt is None:
+        return natural
+    if abi.TEXEL_BYTES.get(int(fmt)) != 4 * tensor.element_size():
+        raise ValueError(f"format {fmt} does not fit a tensor of {tensor.dtype}")
+    return int(fmt)
+
+
+def _any_image(image, fmt=None, srgb=False):
+    if isinstance(image, abi.Image):  # an image the library owns (a G-buffer plane): described already
+        return image
+    color = image.color if isinstance(image, SceneTexture) else image
+    return _strided_image(color, _tensor_format(color, fmt, srgb), 4)
+
+
+def record_copy_image(cmd, source, destination, srcRegion=None, dstRegion=None, srgb=False, srcFormat=None):
+    """Image::recordCopyEntire / recordCopyRect (image.cpp:185-229 -> imageoperations.cpp:141-176): the NEAREST blit of
+    `srcRegion` of `source` onto `dstRegion` of the float16 [h, w, 4] `destination` (RGBA16_SFLOAT), scaling and converting by
+    the rule of include/szg/texture_display.h. `source`: uint8 (RGBA8_UNORM, or RGBA8_SRGB with `srgb`), int16 / uint16
+    (RGBA16_UNORM) or float16 [h, w, 4], a SceneTexture, or an abi.Image (a plane of DeferredShadingPipeline.gbuffer()). Regions are abi.Rect or (x, y, width, height), offsets honoured;
+    None is the whole image."""
+    src = _any_image(source, srcFormat, srgb)
+    dst = _any_image(destination)
+    sr = _as_rect(srcRegion) if srcRegion is not None else abi.Rect(0, 0, src.width, src.height)
+    dr = _as_rect(dstRegion) if dstRegion is not None else abi.Rect(0, 0, dst.width, dst.height)
+    check(lib().szg_record_copy_image(_stream_handle(cmd), C.byref(src), C.byref(dst), sr, dr))
+
+
+def record_clear_color_image(cmd, image, color=(0.0, 0.0, 0.0, 1.0)):
+    """recordClearColorImage (rendercommands.cpp:25): every texel of the float16 (RGBA16_SFLOAT) or int16 / uint16
+    (RGBA16_UNORM) [h, w, 4] tensor or SceneTexture becomes `color`; row padding keeps its bytes."""
+    im = _any_image(image)
+    check(lib().szg_record_clear_color_image(_stream_handle(cmd), C.byref(im), (C.c_float * 4)(*[float(v) for v in color])))
+
+
+# ---------------------------------------------------------------------------
 # Compute-collection pipeline (include/szg/compute_collection.h)
 # ---------------------------------------------------------------------------
-CCMember = namedtuple("CCMember", "name offsetBytes sizeBytes paddedSizeBytes componentType vectorWidth columnCount")
+CCMember =namedtuple("CCMember", "name offsetBytes sizeBytes paddedSizeBytes componentType vectorWidth columnCount")
 CCPushConstant = namedtuple("CCPushConstant", "name sizeBytes paddedSizeBytes layoutOffsetBytes localSize members")
 
 
@@ -1030,6 +1083,18 @@ class UILayer:
         self._keep[out.value] = tensor
         return out.value
 
+    def addTextureView(self, tensor, format=None, filter=abi.SZG_FILTER_LINEAR, address=abi.SZG_UI_ADDRESS_REPEAT, swizzle=None):
+        """ImGui_ImplVulkan_AddTexture of an image VIEW (include/szg/texture_display.h): `tensor` may also be float16
+        [h, w, 4] (RGBA16_SFLOAT), `swizzle` is four abi.SZG_SWIZZLE_* values producing R, G, B, A (None: identity), applied to
+        the filtered sample. Returns an ImTextureID like addTexture."""
+        im = _strided_image(tensor, _tensor_format(tensor, format), 4)
+        view = abi.UITextureView((abi.U32 * 4)(*[int(v) for v in swizzle])) if swizzle is not None else None
+        out = C.c_void_p()
+        check(lib().szg_ui_layer_add_texture_view(self._h, C.byref(im), abi.UISampler(int(filter), int(address)),
+                                                  C.byref(view) if view is not None else None, C.byref(out)))
+        self._keep[out.value] = tensor
+        return out.value
+
     def removeTexture(self, handle):
         check(lib().szg_ui_layer_remove_texture(self._h, C.c_void_p(handle)))
         self._keep.pop(handle, None)
@@ -1073,3 +1138,43 @@ class UILayer:
             self.cleanup()
         except Exception:
             pass
+
+
+class TextureDisplay:
+    """ui/texturedisplay.cpp, the part that runs on the GPU (include/szg/texture_display.h): the Texture Viewer's display
+    image, RGBA16_SFLOAT at `displaySize` (TEXTURE_MAX = 4096^2 in the editor, editor.cpp:47), cleared to opaque black at once
+    as the reference's immediate submit does (:147-162) and registered with the layer NEAREST / CLAMP_TO_BORDER through a
+    view with alpha ONE (:69-80, :104-120). select() is the blit of the picked texture onto the whole image
+    (Image::recordCopyEntire, :164-195), clear() what picking "None" records. The list box, the search and the property table
+    are out of scope: draw `handle` with ui.DrawList.add_image at imageSize()."""
+
+    def __init__(self, uiLayer, displaySize=(4096, 4096), device="cuda:0"):
+        w, h = (int(v) for v in displaySize)
+        self._layer = uiLayer
+        self.width, self.height = w, h
+        self.image = torch.empty((h, w, 4), dtype=torch.float16, device=device)
+        record_clear_color_image(None, self.image)
+        torch.cuda.current_stream().synchronize()
+        self.handle = uiLayer.addTextureView(self.image, filter=abi.SZG_FILTER_NEAREST, address=abi.SZG_UI_ADDRESS_CLAMP_TO_BORDER,
+                                             swizzle=(abi.SZG_SWIZZLE_IDENTITY,) * 3 + (abi.SZG_SWIZZLE_ONE,))
+
+    def select(self, cmd, tensor, srgb=False, format=None, srcRegion=None):
+        """texturedisplay.cpp:164-195: `tensor` (an asset map, uint8 [h, w, 4], sRGB-encoded with `srgb`; or a 16-bit UNORM or
+        float16 image of the frame; a SceneTexture; an abi.Image) stretched onto the whole display image; None is "None" and
+        clears. `srcRegion` (Image::recordCopyRect) shows a part of an image allocated larger than what was drawn."""
+        if tensor is None:
+            return self.clear(cmd)
+        record_copy_image(cmd, tensor, self.image, srcRegion=srcRegion, srgb=srgb, srcFormat=format)
+
+    def clear(self, cmd):
+        record_clear_color_image(cmd, self.image)
+
+    def imageSize(self, contentWidth):
+        """texturedisplay.cpp:291-295: (contentWidth, aspectRatio * contentWidth) with aspectRatio = width / height of the
+        display image. The reference's expression, right for a square image only; kept."""
+        return float(contentWidth), self.width / self.height * float(contentWidth)
+
+    def cleanup(self):
+        if self.handle is not None:
+            self._layer.removeTexture(self.handle)
+            self.handle = None

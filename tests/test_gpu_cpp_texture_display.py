@@ -1,0 +1,63 @@
+"""The C++ mirror of the texture viewer (include/szg/texture_display.hpp: szg::TextureDisplay, UILayer::addTextureView, the
+corner form of szg::recordCopyImageToImage) through its own interface, from a program built with hipcc
+(tests/texture_display/display_texture.cpp) that draws the viewer quad with UILayer::recordDraw over a hand-made draw-data
+struct - against the Python models, byte for byte."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from syzygy_amd import lib
+from tests.native import build as build_native  # this program has its own Makefile, not a target of tests/Makefile
+from tests import texture_display_model as tm
+from tests import ui_layer_cases as uc
+from tests import ui_layer_model as um
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "texture_display")
+
+
+@pytest.mark.parametrize("srgb", [1, 0], ids=["srgb", "unorm"])
+def test_texture_display_from_cpp(tmp_path, srgb):
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
+    lib()  # built and loadable
+    exe = build_native("display_texture", directory=HERE, hashed=[os.path.join(HERE, "display_texture.cpp")])
+    map_extent, display, frame = (6, 3), (16, 16), (40, 30)
+    texels = np.random.default_rng(31).integers(0, 256, (map_extent[1], map_extent[0], 4), dtype=np.uint8)
+    texels[..., 3] = 0  # the viewer is opaque all the same: alpha ONE
+    texels.tofile(tmp_path / "map.bin")
+    p = subprocess.run([exe, str(tmp_path / "map.bin"), *map(str, map_extent + (srgb,) + display + frame), str(tmp_path / "out.bin")],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.returncode, p.stdout + p.stderr)
+    assert p.stdout.strip().splitlines()[-1] == f"OK {frame[0]} {frame[1]}"
+    assert "szg_record_present failed" in p.stderr and "szg_ui_layer_record_draw failed" in p.stderr  # the two refusals, logged
+    raw = np.fromfile(tmp_path / "out.bin", np.uint16)
+    n = frame[0] * frame[1] * 4
+    assert raw.size == 2 * n + display[0] * display[1] * 4
+    got = [raw[:n].reshape(frame[1], frame[0], 4), raw[n:2 * n].reshape(frame[1], frame[0], 4)]
+    shown = raw[2 * n:].reshape(display[1], display[0], 4)
+
+    everything = (0.0, 0.0, float(frame[0]), float(frame[1]))
+    panel, tint = 0xFF503C28, 0xFFC8E6FF
+    vertices = [(2, 2, .5, .5, panel), (38, 2, .5, .5, panel), (38, 28, .5, .5, panel), (2, 28, .5, .5, panel),
+                (12, 4, -0.125, 0, tint), (34, 4, 1, 0, tint), (34, 26, 1, 1.125, tint), (12, 26, -0.125, 1.125, tint)]
+    draw = uc.flat(vertices, [0, 1, 2, 0, 2, 3, 4, 5, 6, 4, 6, 7], [(everything, "font", 0, 0, 6), (everything, "display", 0, 6, 6)], frame)
+    blank = np.zeros((display[1], display[0], 4), np.uint16)
+    selected = tm.copy_image(texels, tm.RGBA8_SRGB if srgb else tm.RGBA8_UNORM, (0, 0) + map_extent, blank, (0, 0) + display)
+    black = blank.copy()
+    black[:] = tm.clear_texel(tm.RGBA16_SFLOAT, (0.0, 0.0, 0.0, 1.0))
+    wants = []
+    for k, content in enumerate((selected, black)):
+        textures = {"font": um.Texture(np.full((1, 1, 4), 255, np.uint8), um.LINEAR, um.REPEAT),
+                    "display": tm.TextureView(content.view(np.float16), um.NEAREST, um.CLAMP_TO_BORDER, (0, 0, 0, tm.ONE))}
+        want = tm.render(np.zeros((frame[1], frame[0], 4), np.uint16), (0, 0) + frame, um.CLEAR, (0, 0, 0, 1), draw, textures)
+        assert np.array_equal(got[k], want), (k, np.argwhere((got[k] != want).any(axis=2))[:5])
+        assert (got[k][..., 3] == 65535).all()
+        wants.append(want)
+    assert (got[0][8:24, 18:32, :3] != 0).any() and (got[1][5:25, 15:33, :3] == 0).all()
+    # frame 3: the UNORM16 output of frame 2 selected into the display through recordSelect(cmd, szg_image)
+    assert np.array_equal(shown, tm.copy_image(wants[1], tm.RGBA16_UNORM, (0, 0) + frame, blank, (0, 0) + display))
