@@ -85,6 +85,12 @@ def lib():
             if "SZG_HIP_LIBRARY" not in os.environ:
                 raise RuntimeError(f"{path} predates include/szg/texture_display.h ({e}); rebuild the library") from e
             print(f"[szg] {path} predates include/szg/texture_display.h ({e}): the texture viewer is unavailable with it", file=sys.stderr)
+        try:
+            abi.bind(handle, abi.LIGHT_TILE_FUNCTIONS)
+        except AttributeError as e:
+            if "SZG_HIP_LIBRARY" not in os.environ:
+                raise RuntimeError(f"{path} predates include/szg/light_tiles.h ({e}); rebuild the library") from e
+            print(f"[szg] {path} predates include/szg/light_tiles.h ({e}): the light tile masks cannot be read back with it", file=sys.stderr)
         _LIB = handle
     return _LIB
 

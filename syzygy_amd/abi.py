@@ -707,6 +707,14 @@ JPEG_FUNCTIONS = {
 }
 
 
+# include/szg/light_tiles.h
+LIGHT_TILE_DIM = 64
+LIGHT_TILE_BATCH = 64
+LIGHT_TILE_FUNCTIONS = {
+    "szg_deferred_debug_light_tile_masks": (C.c_int, [VP, VP, P(C.c_uint64), C.c_uint64, P(U32), P(U32), P(U32)]),
+}
+
+
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""
     for name, (restype, argtypes) in table.items():

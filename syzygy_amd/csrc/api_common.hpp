@@ -215,6 +215,10 @@ struct szg_deferred
     szg::DeviceBuffer<szg_spot_light_packed> d_spots;
     szg::DeviceBuffer<szg::ShadowSlot> d_slots;
     szg::DeviceBuffer<szg::LightRec> d_lightRecs;
+    // per 64 x 64 tile of the capacity extent and per 64 light records one word (k_light_tiles), sized at creation; what the
+    // last lights pass with spot lights wrote is tilesX x tilesY tiles of `batches` words (all 0: none yet)
+    szg::DeviceBuffer<unsigned long long> d_lightTileMasks;
+    unsigned lightTilesX = 0, lightTilesY = 0, lightTileBatches = 0;
     szg::DeviceBuffer<szg::ShadowSlot> d_ownedSlots; // the maps the pipeline allocated itself (never changes after create)
     szg::DeviceBuffer<szg::ShadowGen> d_shadowGen;
     szg::DeviceBuffer<szg_fill_box> d_boxes;

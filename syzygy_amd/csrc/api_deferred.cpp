@@ -3,6 +3,8 @@
 #include <new>
 
 #include "api_common.hpp"
+#include "szg/light_tiles.h"
+#include "szg_light_tiles.hpp"
 
 using namespace szg;
 
@@ -50,6 +52,8 @@ int szg_deferred_create(szg_deferred_t** out, const szg_deferred_desc* desc, int
     SZG_TRY(p->d_spots.alloc(nSpots));
     SZG_TRY(p->d_slots.alloc(nSlots, true));
     SZG_TRY(p->d_lightRecs.alloc((size_t)nSpots + p->maxDirectional));
+    // written in full by k_light_tiles before k_lights reads it: no clear
+    SZG_TRY(p->d_lightTileMasks.alloc(lightTileMaskWords(W, H, (size_t)nSpots + p->maxDirectional)));
     SZG_TRY(p->d_boxes.alloc(p->maxBoxes));
     SZG_TRY(p->d_ownedSlots.alloc(nSlots, true));
     SZG_TRY(p->d_shadowGen.alloc(nSlots));
@@ -298,8 +302,47 @@ int szg_deferred_record_lights(szg_deferred_t* p, void* stream, szg_rect draw_re
     }
     SZG_HIP(szg::launch_light_prep(s, d_directional_lights, directional_light_count, skip, p->d_spots, spot_light_count, p->d_slots,
                                    slotCount, p->d_lightRecs));
+    // Only spot lights can be culled: without one the tile pre-pass is not launched and k_lights visits every light.
+    unsigned const lightCount = nDir + spot_light_count;
+    bool const masked = spot_light_count > 0u;
+    if (masked)
+    {
+        SZG_HIP(szg::launch_light_tiles(s, draw_rect.width, draw_rect.height, t, p->gbuffer, p->d_lightRecs, lightCount,
+                                        p->d_lightTileMasks));
+        unsigned const rows = t.nranks <= 1u ? draw_rect.height : t.local_rows;
+        p->lightTilesX = (draw_rect.width + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM;
+        p->lightTilesY = (rows + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM;
+        p->lightTileBatches = (lightCount + LIGHT_TILE_BATCH - 1u) / LIGHT_TILE_BATCH;
+    }
     SZG_HIP(szg::launch_lights(s, *scene_texture, draw_rect.width, draw_rect.height, t, p->gbuffer, d_cameras, view_camera_index,
-                               p->d_lightRecs, nDir + spot_light_count));
+                               p->d_lightRecs, lightCount, masked ? p->d_lightTileMasks.get() : nullptr));
+    return SZG_OK;
+}
+
+int szg_deferred_debug_light_tile_masks(szg_deferred_t* p, void* stream, uint64_t* out_words, uint64_t capacity_words,
+                                        uint32_t* out_tiles_x, uint32_t* out_tiles_y, uint32_t* out_batches)
+{
+    if (p == nullptr || out_tiles_x == nullptr || out_tiles_y == nullptr || out_batches == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_debug_light_tile_masks: NULL argument");
+    }
+    *out_tiles_x = p->lightTilesX;
+    *out_tiles_y = p->lightTilesY;
+    *out_batches = p->lightTileBatches;
+    uint64_t const words = (uint64_t)p->lightTilesX * p->lightTilesY * p->lightTileBatches;
+    if (out_words == nullptr || words == 0u)
+    {
+        return SZG_OK;
+    }
+    if (capacity_words < words)
+    {
+        return fail(SZG_ERR_CAPACITY, "szg_deferred_debug_light_tile_masks: %llu words, room for %llu", (unsigned long long)words,
+                    (unsigned long long)capacity_words);
+    }
+    DeviceGuard const guard(p->device);
+    hipStream_t const s = static_cast<hipStream_t>(stream);
+    SZG_HIP(hipMemcpyAsync(out_words, p->d_lightTileMasks.get(), words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SZG_HIP(hipStreamSynchronize(s));
     return SZG_OK;
 }
 

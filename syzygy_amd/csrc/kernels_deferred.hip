@@ -5,12 +5,14 @@
 //                    raster state of renderer/pipelines/deferred.cpp:342-392
 //                    (analytic ray cast instead of the fixed-function rasteriser)
 //   k_light_prep   : per-light invariants of deferred/lights.comp:141-161
+//   k_light_tiles  : per 64x64 screen tile, which lights k_lights has to visit
 //   k_lights       : deferred/lights.comp:110-164, fused with the clear of the
 //                    scene colour (deferred.cpp:715-717)
 //   k_compose      : HBM-bound row scatter after the RCCL gather
 
 #include "szg_device.hpp"
 #include "szg_launch.hpp"
+#include "szg_light_tiles.hpp"
 
 namespace szg
 {
@@ -320,9 +322,11 @@ __global__ void k_light_prep(const szg_directional_light_packed* __restrict__ di
 // Per light a lane first runs a division-free conservative test ("surely outside the cone"), then the exact
 // evaluation (the reference's arithmetic, including its exact zero for pixels outside the cone), in
 // ascending light order, so the per-pixel sum adds the same non-zero terms in the same order as the reference
-// loop. Measured on the C3 scene: 29 % of pixel-light pairs are lit (~19 lights per pixel), so the pass is bound
-// by the exact BRDF evaluation rather than by culling; an LDS-staged variant (records copied to LDS once per
-// workgroup, broadcast reads) was measured 20 % slower than scalar loads and dropped.
+// loop. Measured on the C3 scene: 29 % of pixel-light pairs are lit (~19 lights per pixel), so most of the pass is the
+// exact BRDF evaluation; of the 64 lights a wave evaluates 14 for some lane, and the other visits - every lane surely
+// outside the cone - were a fifth of the VALU instructions the kernel issued. k_light_tiles decides those once per 64 x 64 screen tile, and
+// the loop visits only the lights whose bit the tile's mask word has set (profiles/lights_tile_masks.md). An LDS-staged
+// variant (records copied to LDS once per workgroup, broadcast reads) was measured 20 % slower than scalar loads and dropped.
 //
 // A spot light contributes exactly 0 when distance(st, 0.5) / 0.5 >= 1 (lights.comp:84-88). |s - 0.5| > 0.505 on
 // either axis implies that with a 1 % margin, far above any rounding of the exact evaluation, so rejecting there
@@ -337,7 +341,7 @@ SZG_DEV bool leanNumerator(float a) { return a == 0.0f || fabsf(a) >= 0x1p-60f; 
 SZG_DEV float sqrtU(bool lean, float x) { return lean ? sqrtN(x) : sqrtf(x); }
 
 // One light's term of the sum (lights.comp:141-161), exact.
-// `clip`: shadowMatrix * vec4(position, 1), rows x, y, w summed left to right (projectRows below: the cone test and the
+// `clip`: shadowMatrix * vec4(position, 1), rows x, y, w summed left to right (pairCull, szg_light_tiles.hpp: the cone test and the
 // exact evaluation share one evaluation of the three rows; R[k] * 1.0f of the shader's product is R[k] itself)
 // `backCull` (per lane): the pixel's own factors are of ordinary magnitude (k_lights, pixelModerate), so that a term whose last
 // factor clamp(N.L, 0, 1) is 0 is an exact zero and its BRDF (half of the cost of a lit pair) need not be evaluated.
@@ -416,7 +420,7 @@ SZG_DEV V3 lightContribution(const LightRec& L, const Material& m, bool position
         // cull needs no square root. x / 0.5 == x * 2 exactly.
         float const ddx = sx - 0.5f, ddy = sy - 0.5f;
         float const q = SZG_CON(SZG_C_LDOT, ddy, ddy, ddx * ddx); // dot(d, d) of distance()
-        // (an exact zero only while colour * strength / falloff is finite: see falloffAwayFromZero in lightLoop)
+        // (an exact zero only while colour * strength / falloff is finite: see falloffAwayFromZero in pairCull, szg_light_tiles.hpp)
         if (q >= 0.25f && cullable && L.falloffBound * d2 >= 0x1p-28f)
         {
             return splat(0.0f);
@@ -479,13 +483,7 @@ SZG_DEV V3 lightContribution(const LightRec& L, const Material& m, bool position
     return ((m.occlusion * brdf) * spectral) * clampf(ndl, 0.0f, 1.0f);
 }
 
-// The three rows of the shadow matrix the cone test needs (x, y, w) + the spot flag: what is prefetched.
-struct LightCull
-{
-    float rx[4], ry[4], rw[4];
-    float position[3], falloffBound;
-    unsigned isSpot;
-};
+// The three rows of the shadow matrix the cone test needs (x, y, w) + the spot flag (LightCull, szg_light_tiles.hpp).
 SZG_DEV LightCull loadCull(const LightRec* __restrict__ L)
 {
     LightCull c;
@@ -503,69 +501,145 @@ SZG_DEV LightCull loadCull(const LightRec* __restrict__ L)
     c.isSpot = L->isSpot;
     return c;
 }
-// rows x, y and w of shadowMatrix * vec4(p, 1), each summed left to right as the shader does
-SZG_DEV V3 projectRows(const LightCull& c, V3 p)
-{
-    // (M * vec4(p, 1)).row as the oracle's operator* evaluates it: an fma chain over x, y, z, then + m3 * 1
-    float const cx = SZG_CON(SZG_C_MATVEC, c.rx[2], p.z, SZG_CON(SZG_C_MATVEC, c.rx[1], p.y, c.rx[0] * p.x)) + c.rx[3];
-    float const cy = SZG_CON(SZG_C_MATVEC, c.ry[2], p.z, SZG_CON(SZG_C_MATVEC, c.ry[1], p.y, c.ry[0] * p.x)) + c.ry[3];
-    float const cw = SZG_CON(SZG_C_MATVEC, c.rw[2], p.z, SZG_CON(SZG_C_MATVEC, c.rw[1], p.y, c.rw[0] * p.x)) + c.rw[3];
-    return V3{cx, cy, cw};
-}
-SZG_DEV bool surelyOutsideCone(V3 clip)
-{
-    float const cx = clip.x, cy = clip.y, cw = clip.z;
-    float const acw = fabsf(cw);
-    float const ax = fabsf(cx - 0.5f * cw);
-    float const ay = fabsf(cy - 0.5f * cw);
-    // (one axis outside implies q = dx^2 + dy^2 >= 0.25 only if the other axis is a number. It is: the test is only consulted
-    // for a `cullable` pair - every position of the wave finite and <= 2^30, every row of the light <= 2^28 - so the three
-    // projected coordinates are finite numbers below 2^60 and no inf - inf can occur.)
-    return acw > 0.0f && (ax > 0.505f * acw || ay > 0.505f * acw);
-}
-
 // The loop over the lights for one pixel (lights.comp:141-161): terms added in ascending light order.
+// `tileWords` (wave-uniform, may be null): the words k_light_tiles wrote for this pixel's 64 x 64 tile, one per 64 lights, a
+// clear bit = every position of the tile fails pairCull for that light. Read with one scalar load per 64 lights; the set
+// bits are visited from the lowest up, so the sum keeps its order of terms. A wave with a non-finite pixel visits every light,
+// as it ignores the per-pixel cull.
 template <bool OPTIMISTIC>
-SZG_DEV V3 lightLoop(const LightRec* lights, unsigned lightCount, const Material& m, bool positionModerate, V3 viewDirection,
-                     bool waveFinite, bool pixelModerate, float& track)
+SZG_DEV V3 lightLoop(const LightRec* lights, unsigned lightCount, const unsigned long long* __restrict__ tileWords, const Material& m,
+                     bool positionModerate, V3 viewDirection, bool waveFinite, bool pixelModerate, float& track)
 {
     V3 sum = splat(0.0f);
 #pragma unroll 1
-    for (unsigned i = 0; i < lightCount; i++)
+    for (unsigned base = 0, batch = 0; base < lightCount; base += LIGHT_TILE_BATCH, batch++)
     {
-        const LightRec* __restrict__ L = lights + i;
-        LightCull const cur = loadCull(L); // (prefetching light i+1's rows here measured 20 % slower)
-        unsigned const flags = L->leanOK;
-        bool const cullable = waveFinite && (flags & 1u) != 0u;
-        V3 const clip = projectRows(cur, m.position);
-        // A pixel outside the cone contributes (colour * strength / falloff) * 0 * ...: an exact zero ONLY while the quotient
-        // is finite. The falloff factor * (distance / falloffDistance)^2 is 0 AT the light's position and underflows next to
-        // it, and inf * 0 = NaN poisons the pixel in the reference (found in round 3 by a test that puts G-buffer positions
-        // on the lights: rounds 1 and 2 returned 0 there). So the squared distance is formed in front of the cone test, and
-        // the two cone culls - like the back-face cull - require falloffBound * d^2 >= 2^-28 (falloff >= 2^-30 with a factor of
-        // 4 for the roundings): closer pixels are evaluated in full.
-        V3 const toLight = mk3(cur.position[0], cur.position[1], cur.position[2]) - m.position;
-        float const d2 = dotL(toLight, toLight);
-        bool const falloffAwayFromZero = cur.falloffBound * d2 >= 0x1p-28f;
-        if (cur.isSpot != 0u && cullable && falloffAwayFromZero && surelyOutsideCone(clip))
+        unsigned const n = lightCount - base;
+        unsigned long long word = n >= LIGHT_TILE_BATCH ? ~0ull : (1ull << n) - 1ull;
+        if (waveFinite && tileWords != nullptr)
         {
-            continue;
+            word = tileWords[batch]; // (bits of lights past lightCount are clear)
         }
-        if (OPTIMISTIC && (flags & 2u) != 0u)
+#pragma unroll 1
+        while (word != 0ull)
         {
-            sum = sum + lightContribution<true>(*L, m, positionModerate, viewDirection, cullable, clip, pixelModerate, d2, track);
-        }
-        else
-        {
-            sum = sum + lightContribution<false>(*L, m, positionModerate, viewDirection, cullable, clip, pixelModerate, d2, track);
+            unsigned const i = base + (unsigned)__builtin_ctzll(word);
+            word &= word - 1ull;
+            const LightRec* __restrict__ L = lights + i;
+            LightCull const cur = loadCull(L); // (prefetching light i+1's rows here measured 20 % slower)
+            unsigned const flags = L->leanOK;
+            bool const cullable = waveFinite && (flags & 1u) != 0u;
+            // rows x, y, w of the shadow-space position and the squared distance, formed in front of the cone test
+            // (szg_light_tiles.hpp: why the culls ask for falloffBound * d^2 >= 2^-28)
+            PairCull const pc = pairCull(cur, flags, m.position.x, m.position.y, m.position.z);
+            if (waveFinite && pc.skip)
+            {
+                continue;
+            }
+            V3 const clip = mk3(pc.cx, pc.cy, pc.cw);
+            if (OPTIMISTIC && (flags & 2u) != 0u)
+            {
+                sum = sum + lightContribution<true>(*L, m, positionModerate, viewDirection, cullable, clip, pixelModerate, pc.d2, track);
+            }
+            else
+            {
+                sum = sum + lightContribution<false>(*L, m, positionModerate, viewDirection, cullable, clip, pixelModerate, pc.d2, track);
+            }
         }
     }
     return sum;
 }
 
+// ---------------------------------------------------------------------------
+// One workgroup per 64 x 64-pixel tile of the local image (partial at the right and bottom edges): the tile's G-buffer
+// positions - background texels included, which only widens the box - are reduced to an axis-aligned box and the flag "every
+// position finite and <= 2^30"; then wave 0 tests 64 light records at a time against the box, one light per lane
+// (tileMaySkipLight, szg_light_tiles.hpp), and writes one 64-bit word per 64 lights: bit set = visit this light.
+// masks[(tileY * tilesX + tileX) * batches + batch]; every word of every tile of the launch is written, so the storage needs
+// no clear. A non-finite box keeps every bit; so do directional lights and records without flag bit 0.
+__global__ __launch_bounds__(256) void k_light_tiles(szg_image position, unsigned drawW, unsigned localRows,
+                                                     const LightRec* __restrict__ lights, unsigned lightCount,
+                                                     unsigned long long* __restrict__ masks)
+{
+    __shared__ float s_box[4][6];
+    __shared__ unsigned s_bad[4];
+    unsigned const lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned const x = blockIdx.x * LIGHT_TILE_DIM + lane;
+    unsigned const y0 = blockIdx.y * LIGHT_TILE_DIM;
+    float const inf = __builtin_inff();
+    float box[6] = {inf, inf, inf, -inf, -inf, -inf};
+    bool ok = true;
+    if (x < drawW)
+    {
+        for (unsigned r = wave; r < LIGHT_TILE_DIM && y0 + r < localRows; r += 4u)
+        {
+            float4 const p = row_ptr<const float4>(position, y0 + r)[x];
+            ok = ok && fabsf(p.x) <= 0x1p30f && fabsf(p.y) <= 0x1p30f && fabsf(p.z) <= 0x1p30f; // false for a NaN
+            box[0] = fminf(box[0], p.x);
+            box[1] = fminf(box[1], p.y);
+            box[2] = fminf(box[2], p.z);
+            box[3] = fmaxf(box[3], p.x);
+            box[4] = fmaxf(box[4], p.y);
+            box[5] = fmaxf(box[5], p.z);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+    {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1)
+        {
+            float const other = __shfl_xor(box[k], d, 64);
+            box[k] = k < 3 ? fminf(box[k], other) : fmaxf(box[k], other);
+        }
+    }
+    bool const waveOk = waveAll(ok);
+    if (lane == 0u)
+    {
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+        {
+            s_box[wave][k] = box[k];
+        }
+        s_bad[wave] = waveOk ? 0u : 1u;
+    }
+    __syncthreads();
+    if (wave != 0u)
+    {
+        return;
+    }
+    TileBox b;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+    {
+        b.lo[k] = fminf(fminf(s_box[0][k], s_box[1][k]), fminf(s_box[2][k], s_box[3][k]));
+        b.hi[k] = fmaxf(fmaxf(s_box[0][3 + k], s_box[1][3 + k]), fmaxf(s_box[2][3 + k], s_box[3][3 + k]));
+    }
+    b.finite = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) == 0u && b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2];
+    unsigned const batches = (lightCount + LIGHT_TILE_BATCH - 1u) / LIGHT_TILE_BATCH;
+    unsigned long long* out = masks + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * batches;
+    for (unsigned batch = 0; batch < batches; batch++)
+    {
+        unsigned const i = batch * LIGHT_TILE_BATCH + lane;
+        bool visit = false;
+        if (i < lightCount)
+        {
+            const LightRec* __restrict__ L = lights + i;
+            visit = !tileMaySkipLight(loadCull(L), L->leanOK, b);
+        }
+        unsigned long long const word = __builtin_amdgcn_ballot_w64(visit);
+        if (lane == 0u)
+        {
+            out[batch] = word;
+        }
+    }
+}
+
+// `tileMasks` (may be null: no spot lights, nothing to cull): the words of k_light_tiles, `tilesX` tiles per row of tiles.
 __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image debug, GBufferPtrs g, unsigned drawW,
                                                 unsigned localRows, const szg_camera_packed* __restrict__ cameras,
-                                                unsigned cameraIndex, const LightRec* __restrict__ lights, unsigned lightCount)
+                                                unsigned cameraIndex, const LightRec* __restrict__ lights, unsigned lightCount,
+                                                const unsigned long long* __restrict__ tileMasks, unsigned tilesX)
 {
 #ifdef SZG_EXP_LDS_LIGHTS
     // EXPERIMENT (profiles/r03_experiments.md, north_star "LDS-staged light lists"; not built into libszg_hip.so): the light
@@ -629,17 +703,26 @@ __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image de
         // The optimistic pass (lightContribution<true>): every pixel of the wave finite and within 4096 units of the origin.
         bool const tightPixel = pixelFinite && fabsf(m.position.x) <= 0x1p12f && fabsf(m.position.y) <= 0x1p12f && fabsf(m.position.z) <= 0x1p12f &&
                                 inRange(fabsf(m.specularPower), 0x1p-100f, 0x1p20f); // (the exponent half of powLeanOK)
+        // The workgroup's 32 x 8 pixels lie in one 64 x 64 tile: its mask words are found from blockIdx alone (the row
+        // mapping of pixel_of_thread_bottom_up), in scalar registers.
+        const unsigned long long* tileWords = nullptr;
+        if (tileMasks != nullptr)
+        {
+            unsigned const tileX = (blockIdx.x * 32u) / LIGHT_TILE_DIM, tileY = ((gridDim.y - 1u - blockIdx.y) * 8u) / LIGHT_TILE_DIM;
+            unsigned const batches = (lightCount + LIGHT_TILE_BATCH - 1u) / LIGHT_TILE_BATCH;
+            tileWords = tileMasks + (size_t)(tileY * tilesX + tileX) * batches;
+        }
         bool done = false;
         if (waveAll(tightPixel))
         {
             float track = 0x1p100f;
-            sum = lightLoop<true>(SZG_LIGHTS_PTR, lightCount, m, positionModerate, viewDirection, waveFinite, pixelModerate, track);
+            sum = lightLoop<true>(SZG_LIGHTS_PTR, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, track);
             done = waveAll(track >= 0x1p-30f);
         }
         if (!done)
         {
             float unused = 0.0f;
-            sum = lightLoop<false>(SZG_LIGHTS_PTR, lightCount, m, positionModerate, viewDirection, waveFinite, pixelModerate, unused);
+            sum = lightLoop<false>(SZG_LIGHTS_PTR, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, unused);
         }
     }
     row_ptr<uint2>(color, y)[x] = pack_unorm16x4(sum.x, sum.y, sum.z, 1.0f);
@@ -895,7 +978,7 @@ hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* 
 
 hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                          const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, const LightRec* d_lights,
-                         unsigned lightCount)
+                         unsigned lightCount, const unsigned long long* d_tileMasks)
 {
     unsigned const rows = local_rows_of(tile, drawH);
     if (rows == 0u || drawW == 0u)
@@ -904,7 +987,20 @@ hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned
     }
     dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
     hipLaunchKernelGGL(k_lights, grid, dim3(256), 0, s, scene.color, scene.debug_color, gptrs(g), drawW, rows, d_cam, camIndex,
-                       d_lights, lightCount);
+                       d_lights, lightCount, d_tileMasks, (drawW + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_tiles(hipStream_t s, unsigned drawW, unsigned drawH, TileArgs tile, const szg_gbuffer& g,
+                              const LightRec* d_lights, unsigned lightCount, unsigned long long* d_tileMasks)
+{
+    unsigned const rows = local_rows_of(tile, drawH);
+    if (rows == 0u || drawW == 0u || lightCount == 0u)
+    {
+        return hipSuccess;
+    }
+    dim3 const grid((drawW + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM, (rows + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM);
+    hipLaunchKernelGGL(k_light_tiles, grid, dim3(256), 0, s, g.worldPosition, drawW, rows, d_lights, lightCount, d_tileMasks);
     return hipGetLastError();
 }
 

@@ -105,7 +105,12 @@ hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* 
                              unsigned slotCount, LightRec* d_out);
 hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                          const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, const LightRec* d_lights,
-                         unsigned lightCount);
+                         unsigned lightCount, const unsigned long long* d_tileMasks);
+// Per 64 x 64 tile of the local image and per 64 lights one word into `d_tileMasks` (lightTileMaskWords() of
+// szg_light_tiles.hpp sizes it): bit set = k_lights has to visit the light in that tile. launch_lights reads the words when it
+// is handed them (nullptr: every light is visited).
+hipError_t launch_light_tiles(hipStream_t s, unsigned drawW, unsigned drawH, TileArgs tile, const szg_gbuffer& g,
+                              const LightRec* d_lights, unsigned lightCount, unsigned long long* d_tileMasks);
 hipError_t launch_gbuffer_fill(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                                const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, float ground_y,
                                float ground_half_extent, float checker_cell, float ground_roughness,

@@ -681,6 +681,19 @@ class DeferredShadingPipeline:
         im = _strided_image(tensor, abi.SZG_FORMAT_D32_SFLOAT, 1)
         check(lib().szg_deferred_set_shadow_map(self._h, int(index), C.byref(im)))
 
+    def debugLightTileMasks(self, cmd=None):
+        """include/szg/light_tiles.h: the mask words the last lights pass with spot lights wrote, as a uint64 array
+        [tiles_y, tiles_x, batches] (bit i of word b set: the tile visits light record 64 b + i); None before any such pass."""
+        tx, ty, nb = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().szg_deferred_debug_light_tile_masks(self._h, _stream_handle(cmd), None, 0, C.byref(tx), C.byref(ty), C.byref(nb)))
+        n = tx.value * ty.value * nb.value
+        if n == 0:
+            return None
+        words = np.zeros(n, dtype=np.uint64)
+        check(lib().szg_deferred_debug_light_tile_masks(self._h, _stream_handle(cmd), words.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                                        C.byref(tx), C.byref(ty), C.byref(nb)))
+        return words.reshape(ty.value, tx.value, nb.value)
+
     def getConfiguration(self):
         cfg = abi.DeferredConfiguration()
         check(lib().szg_deferred_get_configuration(self._h, C.byref(cfg)))

@@ -1,0 +1,283 @@
+"""GPU: the lights pass with per-tile light masks (k_light_tiles in front of k_lights) against the CPU oracle, bit for bit.
+
+k_light_tiles reduces the G-buffer positions of every 64 x 64 tile to a box and clears, per tile, the bits of the spot lights
+whose cone surely misses the whole box; k_lights visits only the lights whose bit is set. No bit of the image may change.
+The frames are small (two tiles across at most) and hand-made: a patch of the ground plane, a quarter of a unit per pixel,
+under the bench scene's ring of spot lights, so that a tile's box is a few units across and most tiles can drop some lights.
+Each run compares the fp32 debug image (NaN for NaN) and the UNORM16 colour with oracle.binding.lights on the same G-buffer."""
+import numpy as np
+import pytest
+
+from syzygy_amd import abi, scene
+from tests import light_tile_model as lt
+from tests import padded_images as pi
+from tests import stream_order as so
+from tests import util
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(128, 72), (64, 64), (65, 65)]  # 128 x 72: a partial tile in both directions
+SPOTS = [0, 1, 63, 64, 65, 130]
+# (directional lights, dir_skip): one and two lights evaluated, with skip 0 and 1
+DIRS = [(2, 1), (2, 0), (1, 0), (3, 1)]
+CAPACITY_EXTRA = (11, 5)
+SCENE_PADS = (3, 5, 1)
+TILE = abi.LIGHT_TILE_DIM
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
+    from oracle import binding as ob
+    from syzygy_amd import pipelines
+
+    class Ctx:
+        pass
+
+    c = Ctx()
+    c.torch, c.pl, c.ob = torch, pipelines, ob
+    return c
+
+
+def ground_patch(W, H, origin=(-14.0, 6.0), step=0.25):
+    """G-buffer planes of a patch of the ground plane (y = -1, facing up: +y is down), as the fill pass writes geometry."""
+    f = {"diffuse": np.zeros((H, W, 4), np.float16), "specular": np.zeros((H, W, 4), np.float16),
+         "normal": np.zeros((H, W, 4), np.float16), "worldPosition": np.zeros((H, W, 4), np.float32),
+         "occlusionRoughnessMetallic": np.zeros((H, W, 4), np.float16)}
+    xs = (origin[0] + step * np.arange(W)).astype(np.float32)
+    zs = (origin[1] + step * np.arange(H)).astype(np.float32)
+    f["worldPosition"][..., 0] = xs[None, :]
+    f["worldPosition"][..., 1] = -1.0
+    f["worldPosition"][..., 2] = zs[:, None]
+    f["worldPosition"][..., 3] = 1.0
+    grey = np.where((np.add.outer(np.arange(H) // 16, np.arange(W) // 16) % 2) == 0, 200.0 / 255.0, 100.0 / 255.0)
+    f["diffuse"][..., :3] = grey[..., None]
+    f["diffuse"][..., 3] = 1.0
+    f["specular"][...] = f["diffuse"]
+    f["normal"][..., 1] = -1.0
+    f["occlusionRoughnessMetallic"][...] = np.array([1.0, 60.0 / 255.0, 0.0, 1.0], np.float16)
+    return f
+
+
+def host_frame(gpu, W, rows, planes):
+    frame = gpu.ob.HostFrame(W, rows)
+    for name, dst in frame.planes().items():
+        dst[...] = planes[name]
+    return frame
+
+
+def directional(inp, count):
+    third = abi.DirectionalLightPacked.from_buffer_copy(bytes(inp.moon))
+    third.strength = inp.moon.strength * 0.5
+    return [inp.sun, inp.moon, third][:count]
+
+
+def same_bits(got, want):
+    return (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))
+
+
+def run(gpu, W, H, spots, n_spots, n_dirs=2, skip=1, edit=None, tile=None, padded=False, side_stream=False, planes=None, inspect=None):
+    """One lights pass on the GPU and in the oracle on the same G-buffer; asserts equal images. `H` is the global height (the
+    local rows come from `tile`). inspect(deferred, planes, n_evaluated_dirs) runs before the pipeline is destroyed."""
+    rows = H if tile is None else tile.local_rows
+    inp = util.Inputs(W, H, spots=1)
+    planes = ground_patch(W, rows) if planes is None else planes
+    if edit is not None:
+        edit(planes)
+    dirs = directional(inp, n_dirs)
+    frame = host_frame(gpu, W, rows, planes)
+    host_dirs = (abi.DirectionalLightPacked * len(dirs))(*dirs)
+    gpu.ob.lights(frame, inp.rect, tile, None, inp.cam, host_dirs, n_dirs, skip, spots, n_spots, threads=8)
+
+    cameras = gpu.pl.TStagedBuffer(abi.CameraPacked, 1)
+    lights = gpu.pl.TStagedBuffer(abi.DirectionalLightPacked, len(dirs))
+    cameras.push(inp.cam)
+    lights.push(dirs)
+    cameras.recordCopyToDevice()
+    lights.recordCopyToDevice()
+    capacity = (W + CAPACITY_EXTRA[0], rows + CAPACITY_EXTRA[1]) if padded else (W, rows)
+    deferred = gpu.pl.DeferredShadingPipeline(capacity, max_spot_lights=max(n_spots, 1), max_shadow_maps=0)
+    try:
+        if padded:
+            deferred.upload_gbuffer(pi.gbuffer_poison(*capacity))
+            target = pi.PaddedScene(gpu.torch, capacity[0], capacity[1], SCENE_PADS)
+        else:
+            target = gpu.pl.SceneTexture(W, rows, debug=True)
+        deferred.upload_gbuffer(planes)
+        gpu.torch.cuda.synchronize()
+        args = (inp.rect, target, skip, lights, spots if n_spots else None, 0, cameras)
+        if side_stream:
+            with so.side_streams(gpu.torch, 1) as (S,):
+                deferred.recordLights(S, *args, tile=tile)
+                S.synchronize()
+        else:
+            deferred.recordLights(None, *args, tile=tile)
+        gpu.torch.cuda.synchronize()
+        if padded:
+            debug, color = target.debug.inside((W, rows)), target.color.inside((W, rows))
+            target.debug.assert_outside_untouched((W, rows), "debug colour")
+            target.color.assert_outside_untouched((W, rows), "colour")
+        else:
+            debug, color = target.debug.cpu().numpy(), target.color_numpy()
+        bad = np.argwhere(~same_bits(debug, frame.debug).all(axis=-1))
+        assert len(bad) == 0, f"{len(bad)} texels of the debug image differ from the oracle; first (y, x) = {bad[0]}: " \
+                              f"{debug[tuple(bad[0])]} against {frame.debug[tuple(bad[0])]}"
+        assert (color == frame.color).all()
+        if inspect is not None:
+            inspect(deferred, planes, max(n_dirs - skip, 0))
+    finally:
+        deferred.cleanup()
+    return frame
+
+
+@pytest.mark.parametrize("n_spots", SPOTS)
+@pytest.mark.parametrize("size", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
+def test_image_is_bit_identical_to_the_oracle(gpu, size, n_spots):
+    W, H = size
+    n_dirs, skip = DIRS[(SPOTS.index(n_spots) + SIZES.index(size)) % len(DIRS)]
+    frame = run(gpu, W, H, scene.spot_ring(n_spots), n_spots, n_dirs, skip)
+    if n_spots >= 63:
+        assert (frame.debug[..., :3] > 0).any()
+
+
+def check_masks(deferred, planes, n_dirs, n_spots, spots, expect_cleared=True, all_set_tiles=()):
+    """Every cleared bit belongs to a (tile, light) all of whose pixels the per-pixel early-out rejects, computed on the
+    host from the positions the device holds. Returns the number of cleared bits."""
+    rows, W = planes["worldPosition"].shape[:2]
+    masks = deferred.debugLightTileMasks()
+    count = n_dirs + n_spots
+    assert masks is not None and masks.shape == ((rows + TILE - 1) // TILE, (W + TILE - 1) // TILE, (count + 63) // 64)
+    positions = deferred.download_gbuffer(W, rows)["worldPosition"]
+    assert (positions.view(np.uint32) == planes["worldPosition"].view(np.uint32)).all()
+    recs = lt.spot_records(spots, n_spots)
+    cleared = 0
+    for ty in range(masks.shape[0]):
+        for tx in range(masks.shape[1]):
+            p = positions[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE, :3]
+            bits = [(int(masks[ty, tx, i // 64]) >> (i % 64)) & 1 for i in range(masks.shape[2] * 64)]
+            assert all(bits[:n_dirs]), "a directional light keeps its bit"
+            assert not any(bits[count:]), "no bit past the last light"
+            if (ty, tx) in all_set_tiles:
+                assert all(bits[:count]), f"tile {(ty, tx)} must visit every light"
+            for i in range(n_spots):
+                if not bits[n_dirs + i]:
+                    cleared += 1
+                    skip = lt.pair_skip(recs[i], p)
+                    assert skip.all(), f"tile {(ty, tx)}, spot {i}: bit cleared, but {int((~skip).sum())} pixels are not rejected per pixel"
+    print(f"light tile masks: {cleared} of {masks.shape[0] * masks.shape[1] * n_spots} spot bits cleared")
+    if expect_cleared:
+        assert cleared > 0, "the frame was built so that some tile can drop some light"
+    return cleared
+
+
+def test_mask_words_clear_only_what_every_pixel_rejects(gpu):
+    spots = scene.spot_ring(130)
+    run(gpu, 128, 72, spots, 130, 2, 1, inspect=lambda d, planes, nd: check_masks(d, planes, nd, 130, spots))
+
+
+def test_spot_exactly_on_a_gbuffer_position(gpu):
+    """The falloff is 0 at the light: the reference's term there is inf * 0, and the culls must not hide it."""
+    planes = ground_patch(128, 72)
+    at = planes["worldPosition"][40, 100, :3]
+    spots = scene.spot_ring(64)
+    forward = (0.6, 0.0, 0.8)  # along the ground: the pixel itself and most of its tile lie outside the cone
+    spots[5] = scene.make_spot((1.0, 0.5, 0.25), tuple(float(v) for v in at), scene.eulers_from_forward(forward))
+    assert tuple(np.float32(v) for v in spots[5].position[:3]) == tuple(at)
+    run(gpu, 128, 72, spots, 64, planes=planes, inspect=lambda d, p, nd: check_masks(d, p, nd, 64, spots))
+
+
+def test_nan_normal_and_infinite_position_fall_back_to_every_light(gpu):
+    """One pixel with a NaN normal: its wave visits every light (the tile's word may still have clear bits). One pixel with
+    an infinite position: its whole tile keeps every bit (asserted from the words). Under the ring every tile keeps some
+    bits, and any visited light makes the NaN-occlusion pixel NaN: this frame holds the images equal on such inputs, it cannot
+    tell whether a non-finite wave ignored its word. test_a_non_finite_wave_visits_the_lights_its_tile_dropped can."""
+    spots = scene.spot_ring(64)
+
+    def edit(planes):
+        planes["normal"][10, 20, :3] = np.nan            # tile (0, 0); the reference's max() and clamp() absorb it: 0
+        planes["worldPosition"][30, 100, 0] = np.inf     # tile (0, 1)
+        # a NaN occlusion poisons every light's term, the culled ones too (0 * NaN)
+        planes["occlusionRoughnessMetallic"][50, 30, 0] = np.nan
+
+    def inspect(deferred, planes, n_dirs):
+        check_masks(deferred, planes, n_dirs, 64, spots, all_set_tiles={(0, 1)})
+
+    frame = run(gpu, 128, 72, spots, 64, 2, 2, edit=edit, inspect=inspect)
+    assert np.isnan(frame.debug[50, 30, :3]).all() and np.isnan(frame.debug).sum() == 3
+
+
+def spots_that_miss(patch_origin):
+    """Three spot lights 23 units above the ground and 40 units beside a 128 x 72 patch, looking up (+y is down) and a little
+    away from it: every position of the patch lies behind each light (cw < 0) and 60 degrees and more off its axis, far
+    outside the cone and its mirror image."""
+    x, z = patch_origin
+    spots = (abi.SpotLightPacked * 3)()
+    spots[0] = scene.make_spot((1.0, 0.9, 0.8), (x - 40.0, -24.0, z + 8.0), scene.eulers_from_forward((-0.1, -0.99, 0.05)))
+    spots[1] = scene.make_spot((0.8, 1.0, 0.9), (x + 72.0, -24.0, z + 10.0), scene.eulers_from_forward((0.1, -0.99, -0.05)))
+    spots[2] = scene.make_spot((0.9, 0.8, 1.0), (x + 16.0, -24.0, z - 40.0), scene.eulers_from_forward((0.05, -0.99, -0.1)))
+    return spots
+
+
+def test_a_non_finite_wave_visits_the_lights_its_tile_dropped(gpu):
+    """The wave fallback, where it is the only source of a NaN: every spot bit of every tile is clear (asserted from the words
+    read back) and every directional light is skipped, so a wave that honoured its tile's word would visit no light at all
+    and store 0. One pixel has a NaN occlusion: the reference multiplies every light's term by it, culled or not (0 * NaN), so
+    that pixel is NaN in the oracle. It is NaN on the GPU only if the pixel's wave - not finite - ignores the word and visits
+    the lights the tile dropped. The pixel with a NaN normal beside it (another wave) makes its wave fall back too; the
+    reference's max() and clamp() absorb that NaN, and its pixels stay 0."""
+    origin = (-14.0, 6.0)
+    spots = spots_that_miss(origin)
+
+    def edit(planes):
+        planes["occlusionRoughnessMetallic"][50, 30, 0] = np.nan
+        planes["normal"][10, 20, :3] = np.nan
+
+    def inspect(deferred, planes, n_dirs):
+        assert n_dirs == 0
+        masks = deferred.debugLightTileMasks()
+        assert masks.shape == (2, 2, 1) and (masks == 0).all(), f"every spot bit of every tile must be clear: {masks.ravel()}"
+        check_masks(deferred, planes, n_dirs, 3, spots)
+
+    frame = run(gpu, 128, 72, spots, 3, 2, 2, edit=edit, planes=ground_patch(128, 72, origin), inspect=inspect)
+    assert np.isnan(frame.debug[50, 30, :3]).all(), "the oracle's pixel with a NaN occlusion is NaN"
+    assert np.isnan(frame.debug).sum() == 3 and (frame.debug[..., :3][~np.isnan(frame.debug[..., :3])] == 0).all()
+
+
+def test_all_background_tile_beside_a_geometry_tile(gpu):
+    spots = scene.spot_ring(65)
+
+    def edit(planes):
+        for plane in planes.values():
+            plane[:64, 64:] = 0  # the clear values of the G-buffer pass: diffuse.w = 0 is background
+
+    frame = run(gpu, 128, 72, spots, 65, edit=edit, inspect=lambda d, p, nd: check_masks(d, p, nd, 65, spots))
+    assert (frame.color[:64, 64:, :3] == 0).all() and (frame.color[:64, :64, :3] != 0).any()
+
+
+def test_row_tile(gpu):
+    """Rank 1 of 3 with blocks of 8 rows: 72 local rows of a 216-row frame; the tiles are tiles of the LOCAL image."""
+    tile = util.rowtile(216, 8, 1, 3)
+    assert tile.local_rows == 72
+    spots = scene.spot_ring(64)
+    run(gpu, 128, 216, spots, 64, tile=tile, inspect=lambda d, p, nd: check_masks(d, p, nd, 64, spots))
+
+
+def test_images_larger_than_the_draw_extent(gpu):
+    spots = scene.spot_ring(65)
+    run(gpu, 128, 72, spots, 65, padded=True, inspect=lambda d, p, nd: check_masks(d, p, nd, 65, spots))
+
+
+def test_non_blocking_stream(gpu):
+    spots = scene.spot_ring(64)
+    run(gpu, 65, 65, spots, 64, side_stream=True)
+
+
+def test_no_spot_light_launches_no_pre_pass(gpu):
+    """Without a spot light nothing can be culled: the words are not written (none reported), the image is the oracle's."""
+    def inspect(deferred, planes, n_dirs):
+        assert deferred.debugLightTileMasks() is None
+
+    run(gpu, 64, 64, scene.spot_ring(0), 0, 2, 0, inspect=inspect)
