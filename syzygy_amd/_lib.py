@@ -45,52 +45,18 @@ def lib():
         version = handle.szg_abi_version()
         if version != abi.SZG_ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {version}, this package needs {abi.SZG_ABI_VERSION}; rebuild the library")
-        abi.bind(handle, abi.ABI_FUNCTIONS)
-        abi.bind(handle, abi.HOST_FUNCTIONS)
-        abi.bind(handle, abi.RASTER_FUNCTIONS)
-        abi.bind(handle, abi.ASSET_FUNCTIONS)
-        abi.bind(handle, abi.DEBUGLINE_FUNCTIONS)
-        try:
-            abi.bind(handle, abi.PRESENT_FUNCTIONS)
-        except AttributeError as e:
-            # additive entry points do not move the ABI version (include/szg/abi.h): an older build of the same version lacks them
-            raise RuntimeError(f"{path} predates include/szg/present.h ({e}); rebuild the library") from e
-        try:
-            abi.bind(handle, abi.COMPUTE_COLLECTION_FUNCTIONS)
-        except AttributeError as e:
-            raise RuntimeError(f"{path} predates include/szg/compute_collection.h ({e}); rebuild the library") from e
-        try:
-            abi.bind(handle, abi.MIPMAP_FUNCTIONS)
-        except AttributeError as e:
-            if "SZG_HIP_LIBRARY" not in os.environ:
-                raise RuntimeError(f"{path} predates include/szg/mipmaps.h ({e}); rebuild the library") from e
-            # a library named explicitly for a comparison (tools/bench_raster_libraries.py --baseline: a parent commit's build)
-            # may predate the header: everything else works, and a mip entry point raises AttributeError when it is called
-            print(f"[szg] {path} predates include/szg/mipmaps.h ({e}): mip-mapped textures are unavailable with it", file=sys.stderr)
-        try:
-            abi.bind(handle, abi.UI_LAYER_FUNCTIONS)
-        except AttributeError as e:
-            if "SZG_HIP_LIBRARY" not in os.environ:
-                raise RuntimeError(f"{path} predates include/szg/ui_layer.h ({e}); rebuild the library") from e
-            print(f"[szg] {path} predates include/szg/ui_layer.h ({e}): the UI layer pass is unavailable with it", file=sys.stderr)
-        try:
-            abi.bind(handle, abi.JPEG_FUNCTIONS)
-        except AttributeError as e:
-            if "SZG_HIP_LIBRARY" not in os.environ:
-                raise RuntimeError(f"{path} predates include/szg/jpeg.h ({e}); rebuild the library") from e
-            print(f"[szg] {path} predates include/szg/jpeg.h ({e}): JPEG material maps are unavailable with it", file=sys.stderr)
-        try:
-            abi.bind(handle, abi.TEXTURE_DISPLAY_FUNCTIONS)
-        except AttributeError as e:
-            if "SZG_HIP_LIBRARY" not in os.environ:
-                raise RuntimeError(f"{path} predates include/szg/texture_display.h ({e}); rebuild the library") from e
-            print(f"[szg] {path} predates include/szg/texture_display.h ({e}): the texture viewer is unavailable with it", file=sys.stderr)
-        try:
-            abi.bind(handle, abi.LIGHT_TILE_FUNCTIONS)
-        except AttributeError as e:
-            if "SZG_HIP_LIBRARY" not in os.environ:
-                raise RuntimeError(f"{path} predates include/szg/light_tiles.h ({e}); rebuild the library") from e
-            print(f"[szg] {path} predates include/szg/light_tiles.h ({e}): the light tile masks cannot be read back with it", file=sys.stderr)
+        for header, table, notice in abi.BINDINGS:
+            try:
+                abi.bind(handle, table)
+            except AttributeError as e:
+                if header is None:
+                    raise
+                # additive entry points do not move the ABI version (include/szg/abi.h): an older build of the same version lacks them
+                if notice is None or "SZG_HIP_LIBRARY" not in os.environ:
+                    raise RuntimeError(f"{path} predates include/szg/{header} ({e}); rebuild the library") from e
+                # a library named explicitly for a comparison (tools/bench_raster_libraries.py --baseline: a parent commit's build)
+                # may predate the header: everything else works, and one of its entry points raises AttributeError when it is called
+                print(f"[szg] {path} predates include/szg/{header} ({e}): {notice}", file=sys.stderr)
         _LIB = handle
     return _LIB
 

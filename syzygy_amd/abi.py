@@ -715,6 +715,26 @@ LIGHT_TILE_FUNCTIONS = {
 }
 
 
+# What syzygy_amd._lib.lib() binds, in this order: (header, table, notice). A header named here was added without moving the
+# ABI version, so a build of the same version may predate it: lib() then says which header is missing (for the first five,
+# which the version itself covers, a missing export stays an AttributeError). `notice` None: the table must always bind;
+# otherwise a library named through SZG_HIP_LIBRARY may lack it, and `notice` says what is unavailable with it.
+BINDINGS = [
+    (None, ABI_FUNCTIONS, None),
+    (None, HOST_FUNCTIONS, None),
+    (None, RASTER_FUNCTIONS, None),
+    (None, ASSET_FUNCTIONS, None),
+    (None, DEBUGLINE_FUNCTIONS, None),
+    ("present.h", PRESENT_FUNCTIONS, None),
+    ("compute_collection.h", COMPUTE_COLLECTION_FUNCTIONS, None),
+    ("mipmaps.h", MIPMAP_FUNCTIONS, "mip-mapped textures are unavailable with it"),
+    ("ui_layer.h", UI_LAYER_FUNCTIONS, "the UI layer pass is unavailable with it"),
+    ("jpeg.h", JPEG_FUNCTIONS, "JPEG material maps are unavailable with it"),
+    ("texture_display.h", TEXTURE_DISPLAY_FUNCTIONS, "the texture viewer is unavailable with it"),
+    ("light_tiles.h", LIGHT_TILE_FUNCTIONS, "the light tile masks cannot be read back with it"),
+]
+
+
 def bind(lib, table):
     """Attach restype/argtypes from `table` to `lib`; raises AttributeError on a missing export."""
     for name, (restype, argtypes) in table.items():

@@ -1,6 +1,8 @@
 // api_common.hpp — what the api_*.cpp units (the extern "C" boundary of include/szg/abi.h, one unit per pipeline) and
-// szg_comm.cpp share on the host: error reporting, argument checks, the device guard, the owner of device allocations,
-// the staging ring, and the deferred pipeline's object, which api_deferred.cpp and api_raster.cpp both work on.
+// szg_comm.cpp share on the host: error reporting, the argument checks (the predicates image_layout_ok, extents_ok,
+// rect_inside, images_overlap; check_image for a pipeline's images, check_pass_image for the image of a pass without one),
+// the device guard, the owner of device allocations, the staging ring, and the deferred pipeline's object, which
+// api_deferred.cpp and api_raster.cpp both work on.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -8,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -48,9 +51,24 @@ int fail_hip(hipError_t e, const char* what);
 
 unsigned texel_bytes(unsigned fmt);
 szg_image make_image(void* data, unsigned w, unsigned h, unsigned fmt);
+// The conditions every image argument is held to, each written once (api_core.cpp). `data` and `pitch_bytes` are multiples
+// of `bytes`:
+bool rows_aligned(const void* data, unsigned pitch_bytes, unsigned bytes);
+// natural layout: rows of `width` texels of `texel` bytes fit in the pitch, and pitch and data are multiples of `texel`
+bool layout_ok(const void* data, unsigned width, unsigned pitch_bytes, unsigned texel);
+bool image_layout_ok(const szg_image& im); // layout_ok of an image whose format is a known one
+bool extents_ok(const szg_image& im, unsigned min); // both extents in [min, SZG_PRESENT_MAX_EXTENT]
+bool rect_inside(const szg_rect& r, const szg_image& im);
+bool images_overlap(const szg_image& a, const szg_image& b); // the bytes their texels occupy intersect
 // An image must be present, of the expected format, at least w x h, with a
 // pitch that covers its rows and keeps texels naturally aligned.
 bool check_image(const szg_image& im, unsigned fmt, unsigned w, unsigned h, const char* name);
+// An image argument `name` of the pass `me`: present with data, its format one of `formats` (`must` ends the refusal: "must
+// be RGBA16_UNORM"). check_pass_image goes on: extents not above the cap, natural layout, `region` (optional) inside it.
+bool check_image_format(const char* me, const char* name, const szg_image* im, std::initializer_list<unsigned> formats, const char* must);
+bool check_image_layout(const char* me, const char* name, const szg_image& im);
+bool check_pass_image(const char* me, const char* name, const szg_image* im, std::initializer_list<unsigned> formats, const char* must,
+                      const szg_rect* region);
 bool check_gbuffer(const szg_gbuffer* g, unsigned w, unsigned h);
 bool check_scene(const szg_scene_texture* s, unsigned w, unsigned h, bool needDepth);
 // VkRect2D offset: the reference dispatches every pass over the extent only and pushes gbufferOffset = 0

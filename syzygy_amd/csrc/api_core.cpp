@@ -8,6 +8,7 @@
 // record_* call validates shapes on the host, enqueues, and returns; in-stream
 // order replaces the reference's full barriers (imageoperations.cpp:18-33).
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -64,6 +65,37 @@ unsigned texel_bytes(unsigned fmt)
     }
 }
 
+bool rows_aligned(const void* data, unsigned pitch_bytes, unsigned bytes)
+{
+    return pitch_bytes % bytes == 0u && reinterpret_cast<uintptr_t>(data) % bytes == 0u;
+}
+bool layout_ok(const void* data, unsigned width, unsigned pitch_bytes, unsigned texel)
+{
+    return (size_t)pitch_bytes >= (size_t)width * texel && rows_aligned(data, pitch_bytes, texel);
+}
+bool image_layout_ok(const szg_image& im) { return layout_ok(im.data, im.width, im.pitch_bytes, texel_bytes(im.format)); }
+bool extents_ok(const szg_image& im, unsigned min)
+{
+    return im.width >= min && im.height >= min && im.width <= SZG_PRESENT_MAX_EXTENT && im.height <= SZG_PRESENT_MAX_EXTENT;
+}
+bool rect_inside(const szg_rect& r, const szg_image& im)
+{
+    return r.x >= 0 && r.y >= 0 && (uint64_t)r.x + r.width <= im.width && (uint64_t)r.y + r.height <= im.height;
+}
+// the bytes an image's texels occupy: [begin, end)
+static void image_range(const szg_image& im, uintptr_t& begin, uintptr_t& end)
+{
+    begin = reinterpret_cast<uintptr_t>(im.data);
+    end = begin + (im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format));
+}
+bool images_overlap(const szg_image& a, const szg_image& b)
+{
+    uintptr_t ab, ae, bb, be;
+    image_range(a, ab, ae);
+    image_range(b, bb, be);
+    return ab < be && bb < ae;
+}
+
 bool check_image(const szg_image& im, unsigned fmt, unsigned w, unsigned h, const char* name)
 {
     unsigned const tb = texel_bytes(fmt);
@@ -82,10 +114,60 @@ bool check_image(const szg_image& im, unsigned fmt, unsigned w, unsigned h, cons
         fail(SZG_ERR_INVALID_ARGUMENT, "%s: %ux%u smaller than the required %ux%u", name, im.width, im.height, w, h);
         return false;
     }
-    if ((size_t)im.pitch_bytes < (size_t)im.width * tb || im.pitch_bytes % tb != 0 ||
-        (reinterpret_cast<uintptr_t>(im.data) % tb) != 0)
+    if (!image_layout_ok(im))
     {
         fail(SZG_ERR_INVALID_ARGUMENT, "%s: pitch %u / alignment invalid for %u-byte texels", name, im.pitch_bytes, tb);
+        return false;
+    }
+    return true;
+}
+
+bool check_image_format(const char* me, const char* name, const szg_image* im, std::initializer_list<unsigned> formats, const char* must)
+{
+    if (im == nullptr || im->data == nullptr)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image or its data is NULL", me, name);
+        return false;
+    }
+    if (std::find(formats.begin(), formats.end(), im->format) == formats.end())
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s format %u, %s", me, name, im->format, must);
+        return false;
+    }
+    return true;
+}
+
+bool check_image_layout(const char* me, const char* name, const szg_image& im)
+{
+    if (!image_layout_ok(im))
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s pitch %u / alignment invalid for %u texels of %u bytes", me, name, im.pitch_bytes, im.width,
+             texel_bytes(im.format));
+        return false;
+    }
+    return true;
+}
+
+bool check_pass_image(const char* me, const char* name, const szg_image* im, std::initializer_list<unsigned> formats, const char* must,
+                      const szg_rect* region)
+{
+    if (!check_image_format(me, name, im, formats, must))
+    {
+        return false;
+    }
+    if (!extents_ok(*im, 0u))
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image %ux%u exceeds %u texels", me, name, im->width, im->height, SZG_PRESENT_MAX_EXTENT);
+        return false;
+    }
+    if (!check_image_layout(me, name, *im))
+    {
+        return false;
+    }
+    if (region != nullptr && !rect_inside(*region, *im))
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s region (%d, %d) %ux%u leaves the %ux%u image", me, name, region->x, region->y, region->width,
+             region->height, im->width, im->height);
         return false;
     }
     return true;
@@ -253,8 +335,8 @@ int szg_compose_rowtiles(void* stream, const void* gathered, size_t tile_stride_
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
-    if ((width * 8u) % 16u != 0u || tile_stride_bytes % 16u != 0u || dst->pitch_bytes % 16u != 0u ||
-        reinterpret_cast<uintptr_t>(gathered) % 16u != 0u || reinterpret_cast<uintptr_t>(dst->data) % 16u != 0u)
+    if ((width * 8u) % 16u != 0u || tile_stride_bytes % 16u != 0u || reinterpret_cast<uintptr_t>(gathered) % 16u != 0u ||
+        !rows_aligned(dst->data, dst->pitch_bytes, 16u))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_compose_rowtiles: rows must be 16-byte multiples and 16-byte aligned");
     }

@@ -6,6 +6,8 @@
 
 using namespace szg;
 
+static_assert(SZG_COMPUTE_COLLECTION_MAX_EXTENT == SZG_PRESENT_MAX_EXTENT, "extents_ok (api_core.cpp) holds both passes to one cap");
+
 namespace
 {
 // Per-device OETF tables (one per transfer function), built on first use by k_oetf_table and kept for the life of
@@ -61,56 +63,6 @@ int oetf_table(hipStream_t s, unsigned function, const unsigned short** out)
     return SZG_OK;
 }
 
-// One image of the blit: present, of an accepted format, not above the extent cap, rows inside the pitch, and the region
-// inside the image. Everything here runs on the host, before anything is launched.
-bool check_present_image(const szg_image* im, const szg_rect& r, bool isSource, const char* name)
-{
-    if (im == nullptr || im->data == nullptr)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s image or its data is NULL", name);
-        return false;
-    }
-    bool const formatOk = isSource ? im->format == SZG_FORMAT_RGBA16_UNORM
-                                   : (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_BGRA8_UNORM ||
-                                      im->format == SZG_FORMAT_A2B10G10R10_UNORM);
-    if (!formatOk)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT,
-             isSource ? "szg_record_present: %s format %u, the source must be RGBA16_UNORM"
-                      : "szg_record_present: %s format %u, the destination must be RGBA8_UNORM, BGRA8_UNORM or A2B10G10R10_UNORM",
-             name, im->format);
-        return false;
-    }
-    if (im->width > SZG_PRESENT_MAX_EXTENT || im->height > SZG_PRESENT_MAX_EXTENT)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s image %ux%u exceeds %u texels", name, im->width, im->height,
-             SZG_PRESENT_MAX_EXTENT);
-        return false;
-    }
-    unsigned const tb = texel_bytes(im->format);
-    if ((size_t)im->pitch_bytes < (size_t)im->width * tb || im->pitch_bytes % tb != 0u ||
-        reinterpret_cast<uintptr_t>(im->data) % tb != 0u)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s pitch %u / alignment invalid for %u texels of %u bytes", name,
-             im->pitch_bytes, im->width, tb);
-        return false;
-    }
-    if (r.x < 0 || r.y < 0 || (uint64_t)r.x + r.width > im->width || (uint64_t)r.y + r.height > im->height)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: %s region (%d, %d) %ux%u leaves the %ux%u image", name, r.x, r.y,
-             r.width, r.height, im->width, im->height);
-        return false;
-    }
-    return true;
-}
-// the bytes an image's texels occupy: [begin, end)
-void image_range(const szg_image& im, uintptr_t& begin, uintptr_t& end)
-{
-    begin = reinterpret_cast<uintptr_t>(im.data);
-    size_t const bytes = im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format);
-    end = begin + bytes;
-}
-
 // What ShaderReflectionData::PushConstant holds for the four programs of renderer.cpp:238-243. Static tables; their truth is
 // checked against the reference's binaries by tests/test_compute_collection_reflection.py, not trusted.
 #define SZG_CC_PREFIX_MEMBERS                                                                                                  \
@@ -161,7 +113,7 @@ int szg_record_oetf(void* stream, const szg_image* image, uint32_t width, uint32
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
-    if (image->pitch_bytes % 16u != 0u || reinterpret_cast<uintptr_t>(image->data) % 16u != 0u)
+    if (!rows_aligned(image->data, image->pitch_bytes, 16u))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_oetf: image rows must be 16-byte aligned");
     }
@@ -181,7 +133,10 @@ int szg_record_present(void* stream, const szg_image* src, const szg_image* dst,
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: info is NULL");
     }
-    if (!check_present_image(src, info->src_region, true, "source") || !check_present_image(dst, info->dst_region, false, "destination"))
+    static const char* const me = "szg_record_present";
+    if (!check_pass_image(me, "source", src, {SZG_FORMAT_RGBA16_UNORM}, "the source must be RGBA16_UNORM", &info->src_region) ||
+        !check_pass_image(me, "destination", dst, {SZG_FORMAT_RGBA8_UNORM, SZG_FORMAT_BGRA8_UNORM, SZG_FORMAT_A2B10G10R10_UNORM},
+                          "the destination must be RGBA8_UNORM, BGRA8_UNORM or A2B10G10R10_UNORM", &info->dst_region))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
@@ -193,10 +148,7 @@ int szg_record_present(void* stream, const szg_image* src, const szg_image* dst,
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: unknown encode %u", info->encode);
     }
-    uintptr_t sb, se, db, de;
-    image_range(*src, sb, se);
-    image_range(*dst, db, de);
-    if (sb < de && db < se)
+    if (images_overlap(*src, *dst))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_present: source and destination images overlap in memory");
     }
@@ -257,13 +209,12 @@ int szg_record_compute_collection(void* stream, uint32_t shader_index, const voi
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: colour format %u, must be RGBA16_UNORM", color->format);
     }
-    if (color->width > SZG_COMPUTE_COLLECTION_MAX_EXTENT || color->height > SZG_COMPUTE_COLLECTION_MAX_EXTENT)
+    if (!extents_ok(*color, 0u))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: colour image %ux%u exceeds %u texels", color->width,
                     color->height, SZG_COMPUTE_COLLECTION_MAX_EXTENT);
     }
-    if ((size_t)color->pitch_bytes < (size_t)color->width * 8u || color->pitch_bytes % 8u != 0u ||
-        reinterpret_cast<uintptr_t>(color->data) % 8u != 0u)
+    if (!image_layout_ok(*color))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_compute_collection: pitch %u / alignment invalid for %u texels of 8 bytes",
                     color->pitch_bytes, color->width);

@@ -70,7 +70,7 @@ int szg_record_jpeg_reconstruct(void* stream, const szg_jpeg_frame* frame, void*
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_jpeg_reconstruct: dst %ux%u is smaller than the frame %ux%u", dst->width, dst->height,
                     frame->width, frame->height);
     }
-    if ((size_t)dst->pitch_bytes < (size_t)dst->width * 4u || dst->pitch_bytes % 4u != 0u)
+    if (!image_layout_ok(*dst)) // (the alignment of dst->data was refused above, under its own sentence)
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_jpeg_reconstruct: dst pitch %u is smaller than a row of %u texels or no multiple of 4",
                     dst->pitch_bytes, dst->width);

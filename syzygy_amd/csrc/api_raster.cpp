@@ -59,8 +59,9 @@ int collect_draws(const char* who, const szg_mesh_instanced* meshes, uint32_t me
             d.tex[2] = surf.material.orm;
             for (szg_texture const& t : d.tex)
             {
+                // (no refusal of a t.data that is not aligned to its 4-byte texels: layout_ok is given no pointer)
                 if (t.data != nullptr && (t.width == 0u || t.height == 0u || t.width > 32768u || t.height > 32768u ||
-                                          t.pitch_bytes < t.width * 4u || t.pitch_bytes % 4u != 0u))
+                                          !layout_ok(nullptr, t.width, t.pitch_bytes, 4u)))
                 {
                     return fail(SZG_ERR_INVALID_ARGUMENT, "%s: mesh %u surface %u has a malformed texture", who, i, k);
                 }
@@ -258,7 +259,7 @@ int szg_record_generate_mipmaps(void* stream, const szg_texture* level0, void* d
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: extent %ux%u outside 1..32768", level0->width, level0->height);
     }
-    if (level0->pitch_bytes < level0->width * 4u || level0->pitch_bytes % 4u != 0u)
+    if (!layout_ok(nullptr, level0->width, level0->pitch_bytes, 4u)) // the pointer's alignment has its own sentence below
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_generate_mipmaps: pitch %u is smaller than a row of %u texels or no multiple of 4",
                     level0->pitch_bytes, level0->width);

@@ -8,82 +8,20 @@ using namespace szg;
 
 static_assert(SZG_FORMAT_RGBA8_SRGB == 8, "szg/abi.h: the format values are part of the ABI");
 
-namespace
-{
-// One image of the copy or the clear: present, not above the extent cap, rows inside the pitch, texels naturally aligned.
-// The format is the caller's to check first. Everything here runs on the host, before anything is launched.
-bool check_layout(const char* me, const szg_image* im, const char* name)
-{
-    if (im->width > SZG_PRESENT_MAX_EXTENT || im->height > SZG_PRESENT_MAX_EXTENT)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image %ux%u exceeds %u texels", me, name, im->width, im->height, SZG_PRESENT_MAX_EXTENT);
-        return false;
-    }
-    unsigned const tb = texel_bytes(im->format);
-    if ((size_t)im->pitch_bytes < (size_t)im->width * tb || im->pitch_bytes % tb != 0u || reinterpret_cast<uintptr_t>(im->data) % tb != 0u)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s pitch %u / alignment invalid for %u texels of %u bytes", me, name, im->pitch_bytes, im->width,
-             tb);
-        return false;
-    }
-    return true;
-}
-
-bool check_copy_image(const szg_image* im, const szg_rect& r, bool isSource, const char* name)
-{
-    static const char* const me = "szg_record_copy_image";
-    if (im == nullptr || im->data == nullptr)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image or its data is NULL", me, name);
-        return false;
-    }
-    bool const formatOk = isSource ? (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_RGBA8_SRGB ||
-                                      im->format == SZG_FORMAT_RGBA16_UNORM || im->format == SZG_FORMAT_RGBA16_SFLOAT)
-                                   : im->format == SZG_FORMAT_RGBA16_SFLOAT;
-    if (!formatOk)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT,
-             isSource ? "%s: %s format %u, the source must be RGBA8_UNORM, RGBA8_SRGB, RGBA16_UNORM or RGBA16_SFLOAT"
-                      : "%s: %s format %u, the destination must be RGBA16_SFLOAT",
-             me, name, im->format);
-        return false;
-    }
-    if (!check_layout(me, im, name))
-    {
-        return false;
-    }
-    if (r.x < 0 || r.y < 0 || (uint64_t)r.x + r.width > im->width || (uint64_t)r.y + r.height > im->height)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s region (%d, %d) %ux%u leaves the %ux%u image", me, name, r.x, r.y, r.width, r.height, im->width,
-             im->height);
-        return false;
-    }
-    return true;
-}
-
-// the bytes an image's texels occupy: [begin, end)
-void image_range(const szg_image& im, uintptr_t& begin, uintptr_t& end)
-{
-    begin = reinterpret_cast<uintptr_t>(im.data);
-    size_t const bytes = im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format);
-    end = begin + bytes;
-}
-} // namespace
-
 extern "C" {
 
 int szg_record_copy_image(void* stream, const szg_image* src, const szg_image* dst, szg_rect src_region, szg_rect dst_region)
 {
-    if (!check_copy_image(src, src_region, true, "source") || !check_copy_image(dst, dst_region, false, "destination"))
+    static const char* const me = "szg_record_copy_image";
+    if (!check_pass_image(me, "source", src, {SZG_FORMAT_RGBA8_UNORM, SZG_FORMAT_RGBA8_SRGB, SZG_FORMAT_RGBA16_UNORM, SZG_FORMAT_RGBA16_SFLOAT},
+                          "the source must be RGBA8_UNORM, RGBA8_SRGB, RGBA16_UNORM or RGBA16_SFLOAT", &src_region) ||
+        !check_pass_image(me, "destination", dst, {SZG_FORMAT_RGBA16_SFLOAT}, "the destination must be RGBA16_SFLOAT", &dst_region))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
-    uintptr_t sb, se, db, de;
-    image_range(*src, sb, se);
-    image_range(*dst, db, de);
-    if (sb < de && db < se)
+    if (images_overlap(*src, *dst))
     {
-        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_record_copy_image: source and destination images overlap in memory");
+        return fail(SZG_ERR_INVALID_ARGUMENT, "%s: source and destination images overlap in memory", me);
     }
     if (src_region.width == 0u || src_region.height == 0u || dst_region.width == 0u || dst_region.height == 0u)
     {
@@ -104,7 +42,8 @@ int szg_record_clear_color_image(void* stream, const szg_image* image, const flo
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "%s: image format %u, must be RGBA16_SFLOAT or RGBA16_UNORM", me, image->format);
     }
-    if (!check_layout(me, image, "the"))
+    // the NULL and format refusals above have this call's own wording; what is left here is the extent cap and the layout
+    if (!check_pass_image(me, "the", image, {SZG_FORMAT_RGBA16_SFLOAT, SZG_FORMAT_RGBA16_UNORM}, "", nullptr))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }

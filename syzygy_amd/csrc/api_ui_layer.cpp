@@ -33,48 +33,21 @@ struct szg_ui_layer
 
 namespace
 {
-void image_bytes(const szg_image& im, uintptr_t& begin, uintptr_t& end)
+// the output or a texture: present, of one of `formats`, extents in [min, cap], rows inside the pitch, texels naturally aligned
+bool check_ui_image(const char* caller, const char* name, const szg_image* im, unsigned min, std::initializer_list<unsigned> formats,
+                    const char* must)
 {
-    begin = reinterpret_cast<uintptr_t>(im.data);
-    end = begin + (im.height == 0u ? 0u : (size_t)(im.height - 1u) * im.pitch_bytes + (size_t)im.width * texel_bytes(im.format));
-}
-
-// present, of an accepted format (the output: RGBA16_UNORM; a texture: that or RGBA8_UNORM, and with `allowHalf`, the
-// textures of szg_ui_layer_add_texture_view, RGBA16_SFLOAT), not above the extent cap, rows inside the pitch, texels naturally
-// aligned
-bool check_ui_image(const char* caller, const szg_image* im, bool isOutput, const char* name, bool allowHalf = false)
-{
-    if (im == nullptr || im->data == nullptr)
+    if (!check_image_format(caller, name, im, formats, must))
     {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image or its data is NULL", caller, name);
         return false;
     }
-    bool const formatOk = isOutput ? im->format == SZG_FORMAT_RGBA16_UNORM
-                                   : (im->format == SZG_FORMAT_RGBA8_UNORM || im->format == SZG_FORMAT_RGBA16_UNORM ||
-                                      (allowHalf && im->format == SZG_FORMAT_RGBA16_SFLOAT));
-    if (!formatOk)
+    if (!extents_ok(*im, min))
     {
-        fail(SZG_ERR_INVALID_ARGUMENT,
-             isOutput    ? "%s: %s format %u, must be RGBA16_UNORM"
-             : allowHalf ? "%s: %s format %u, must be RGBA8_UNORM, RGBA16_UNORM or RGBA16_SFLOAT"
-                         : "%s: %s format %u, must be RGBA8_UNORM or RGBA16_UNORM",
-             caller, name, im->format);
+        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image %ux%u, extents must lie in [%u, %u]", caller, name, im->width, im->height, min,
+             SZG_PRESENT_MAX_EXTENT);
         return false;
     }
-    if (im->width > SZG_PRESENT_MAX_EXTENT || im->height > SZG_PRESENT_MAX_EXTENT || (!isOutput && (im->width == 0u || im->height == 0u)))
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s image %ux%u, extents must lie in [%u, %u]", caller, name, im->width, im->height,
-             isOutput ? 0u : 1u, SZG_PRESENT_MAX_EXTENT);
-        return false;
-    }
-    unsigned const tb = texel_bytes(im->format);
-    if ((size_t)im->pitch_bytes < (size_t)im->width * tb || im->pitch_bytes % tb != 0u || reinterpret_cast<uintptr_t>(im->data) % tb != 0u)
-    {
-        fail(SZG_ERR_INVALID_ARGUMENT, "%s: %s pitch %u / alignment invalid for %u texels of %u bytes", caller, name, im->pitch_bytes,
-             im->width, tb);
-        return false;
-    }
-    return true;
+    return check_image_layout(caller, name, *im);
 }
 
 szg_ui_texture* find_texture(szg_ui_layer* layer, const szg_ui_texture* t)
@@ -112,7 +85,11 @@ int add_texture(const char* me, szg_ui_layer* layer, const szg_image* image, szg
         return fail(SZG_ERR_INVALID_ARGUMENT, "%s: NULL argument", me);
     }
     *out = nullptr;
-    if (!check_ui_image(me, image, false, "texture", allowHalf))
+    bool const imageOk = allowHalf ? check_ui_image(me, "texture", image, 1u, {SZG_FORMAT_RGBA8_UNORM, SZG_FORMAT_RGBA16_UNORM, SZG_FORMAT_RGBA16_SFLOAT},
+                                                    "must be RGBA8_UNORM, RGBA16_UNORM or RGBA16_SFLOAT")
+                                   : check_ui_image(me, "texture", image, 1u, {SZG_FORMAT_RGBA8_UNORM, SZG_FORMAT_RGBA16_UNORM},
+                                                    "must be RGBA8_UNORM or RGBA16_UNORM");
+    if (!imageOk)
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
@@ -252,12 +229,12 @@ int szg_ui_layer_record_draw(szg_ui_layer_t* layer, void* stream, const szg_imag
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "%s: NULL argument", me);
     }
-    if (!check_ui_image(me, output, true, "output"))
+    if (!check_ui_image(me, "output", output, 0u, {SZG_FORMAT_RGBA16_UNORM}, "must be RGBA16_UNORM"))
     {
         return SZG_ERR_INVALID_ARGUMENT;
     }
     szg_rect const& ra = render_area;
-    if (ra.x < 0 || ra.y < 0 || (uint64_t)ra.x + ra.width > output->width || (uint64_t)ra.y + ra.height > output->height)
+    if (!rect_inside(ra, *output))
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "%s: render area (%d, %d) %ux%u leaves the %ux%u image", me, ra.x, ra.y, ra.width, ra.height,
                     output->width, output->height);
@@ -287,8 +264,6 @@ int szg_ui_layer_record_draw(szg_ui_layer_t* layer, void* stream, const szg_imag
     {
         return fail(SZG_ERR_CAPACITY, "%s: %u commands, capacity %u", me, dd.command_count, layer->commandCapacity);
     }
-    uintptr_t ob, oe;
-    image_bytes(*output, ob, oe);
     // VIEWPORT
     int const fbw = trunc_saturated(dd.display_size[0] * dd.framebuffer_scale[0]);
     int const fbh = trunc_saturated(dd.display_size[1] * dd.framebuffer_scale[1]);
@@ -318,9 +293,7 @@ int szg_ui_layer_record_draw(szg_ui_layer_t* layer, void* stream, const szg_imag
         {
             return fail(SZG_ERR_INVALID_ARGUMENT, "%s: the texture of command %u is not this layer's", me, i);
         }
-        uintptr_t tb, te;
-        image_bytes(tex->image, tb, te);
-        if (tb < oe && ob < te)
+        if (images_overlap(tex->image, *output))
         {
             return fail(SZG_ERR_INVALID_ARGUMENT, "%s: the texture of command %u overlaps the output image in memory", me, i);
         }

@@ -15,6 +15,7 @@ import pytest
 from syzygy_amd import abi, lib, library_path, pipelines
 from tests import compute_collection_model as model
 from tests import native
+from tests.texture_display_cases import image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "compute_collection_reflection.json")
@@ -163,45 +164,52 @@ def test_cpp_accessors_agree_with_the_reflection_of_the_binaries(golden, tmp_pat
                 assert (m["vector_width"], m["column_count"]) == (want["vector"], 1)
 
 
-def _image(width=64, height=32, pitch=None, fmt=abi.SZG_FORMAT_RGBA16_UNORM, data=0x1000):
-    # `data` is never dereferenced: every call below is refused on the host, before anything is launched
-    im = abi.Image()
-    im.data, im.width, im.height, im.format = data, width, height, fmt
-    im.pitch_bytes = width * 8 if pitch is None else pitch
-    return im
+def record_refusals(data=0x1000):
+    """(name, arguments of szg_record_compute_collection after the stream, text the message must hold or None) of every
+    refusal, for a 64x32 RGBA16_UNORM image at address `data`, which is never dereferenced: every call is refused on the host,
+    before anything is launched."""
+    U16 = abi.SZG_FORMAT_RGBA16_UNORM
+    blocks = [bytes(n) for n in (80, 48, 80, 208)]
+    ok = image(64, 32, U16, data)
+    cases = [
+        ("NULL bytes", (1, None, 48, ok, 40, 24), None),
+        ("NULL image", (1, blocks[1], 48, None, 40, 24), None),
+        ("NULL data", (1, blocks[1], 48, image(64, 32, U16, None), 40, 24), None),
+        ("index 4", (4, blocks[3], 208, ok, 40, 24), b"the collection has 4 programs"),
+        ("index 0xFFFFFFFF", (0xFFFFFFFF, blocks[3], 208, ok, 40, 24), None),
+    ]
+    for index, size in enumerate((80, 48, 80, 208)):  # a byte count other than the padded block size
+        for wrong in (0, 16, size - 4, size + 4, 256):
+            cases.append((f"program {index} with {wrong} bytes", (index, bytes(256), wrong, ok, 40, 24), None))
+    for fmt in (abi.SZG_FORMAT_RGBA16_SFLOAT, abi.SZG_FORMAT_RGBA32_SFLOAT, abi.SZG_FORMAT_RGBA8_UNORM, abi.SZG_FORMAT_UNDEFINED):
+        cases.append((f"format {fmt}", (1, blocks[1], 48, image(64, 32, fmt, data, pitch=64 * 8), 40, 24), b"RGBA16_UNORM"))
+    cases += [
+        ("pitch below the row", (1, blocks[1], 48, image(64, 32, U16, data, pitch=64 * 8 - 8), 40, 24), None),
+        ("pitch not a texel multiple", (1, blocks[1], 48, image(64, 32, U16, data, pitch=64 * 8 + 4), 40, 24), None),
+        ("data misaligned", (1, blocks[1], 48, image(64, 32, U16, data + 4), 40, 24), None),
+    ]
+    for w, h in ((0, 24), (40, 0), (0, 0), (65, 24), (40, 33), (0xFFFFFFFF, 24)):  # empty, or leaves the image
+        cases.append((f"extent {w}x{h}", (1, blocks[1], 48, ok, w, h), None))
+    big = abi.SZG_COMPUTE_COLLECTION_MAX_EXTENT + 1
+    cases.append(("wider than the cap", (1, blocks[1], 48, image(big, 8, U16, data), 40, 8), b"exceeds"))
+    cases.append(("higher than the cap", (1, blocks[1], 48, image(8, big, U16, data), 8, 8), b"exceeds"))
+    return cases
+
+
+def record_refusal(case):
+    """Make the call of one of record_refusals(): (status, last-error text)."""
+    index, block, count, im, w, h = case[1]
+    status = lib().szg_record_compute_collection(None, index, block, count, C.byref(im) if im is not None else None, w, h)
+    return status, lib().szg_last_error()
 
 
 def test_every_refusal_returns_invalid_argument_without_a_device():
     L = lib()
-    rec = L.szg_record_compute_collection
     bad = abi.SZG_ERR_INVALID_ARGUMENT
-    blocks = [bytes(n) for n in (80, 48, 80, 208)]
-    ok = _image()
-
-    def refused(*args):
-        status = rec(None, *args)
-        text = L.szg_last_error()
-        assert status == bad and b"szg_record_compute_collection" in text, (status, text)
-        return text
-
-    refused(1, None, 48, C.byref(ok), 40, 24)  # NULL bytes
-    refused(1, blocks[1], 48, None, 40, 24)  # NULL image
-    refused(1, blocks[1], 48, C.byref(_image(data=None)), 40, 24)  # NULL data
-    assert b"the collection has 4 programs" in refused(4, blocks[3], 208, C.byref(ok), 40, 24)  # index >= 4
-    refused(0xFFFFFFFF, blocks[3], 208, C.byref(ok), 40, 24)
-    for index, size in enumerate((80, 48, 80, 208)):  # a byte count other than the padded block size
-        for wrong in (0, 16, size - 4, size + 4, 256):
-            refused(index, bytes(256), wrong, C.byref(ok), 40, 24)
-    for fmt in (abi.SZG_FORMAT_RGBA16_SFLOAT, abi.SZG_FORMAT_RGBA32_SFLOAT, abi.SZG_FORMAT_RGBA8_UNORM, abi.SZG_FORMAT_UNDEFINED):
-        assert b"RGBA16_UNORM" in refused(1, blocks[1], 48, C.byref(_image(fmt=fmt)), 40, 24)
-    refused(1, blocks[1], 48, C.byref(_image(pitch=64 * 8 - 8)), 40, 24)  # pitch smaller than a row
-    refused(1, blocks[1], 48, C.byref(_image(pitch=64 * 8 + 4)), 40, 24)  # pitch not a multiple of the texel
-    refused(1, blocks[1], 48, C.byref(_image(data=0x1004)), 40, 24)  # data not texel-aligned
-    for w, h in ((0, 24), (40, 0), (0, 0), (65, 24), (40, 33), (0xFFFFFFFF, 24)):  # empty, or leaves the image
-        refused(1, blocks[1], 48, C.byref(ok), w, h)
-    big = abi.SZG_COMPUTE_COLLECTION_MAX_EXTENT + 1
-    assert b"exceeds" in refused(1, blocks[1], 48, C.byref(_image(width=big, height=8)), 40, 8)
-    assert b"exceeds" in refused(1, blocks[1], 48, C.byref(_image(width=8, height=big)), 8, 8)
+    for case in record_refusals():
+        status, text = record_refusal(case)
+        assert status == bad and b"szg_record_compute_collection" in text, (case[0], status, text)
+        assert case[2] is None or case[2] in text, (case[0], text)
     # the reflection entry point
     r = abi.CCReflection()
     assert L.szg_compute_collection_reflect(4, C.byref(r)) == bad and L.szg_compute_collection_reflect(0, None) == bad

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import present_model as pm
+from tests.texture_display_cases import image as fake_image
 from syzygy_amd import abi, lib, library_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -249,11 +250,6 @@ def test_present_constants_and_struct_match_the_header():
     assert C.sizeof(abi.PresentInfo) == 40 and abi.PresentInfo.filter.offset == 32 and abi.PresentInfo.encode.offset == 36
     # the present pass is additive (one new symbol, new format values behind the old ones): the ABI version does not move
     assert lib().szg_abi_version() == abi.SZG_ABI_VERSION
-
-
-def fake_image(width, height, fmt, address, pitch=None):
-    """An szg_image over memory that is never touched: refusals are decided on the host before anything is launched."""
-    return abi.Image(address, width, height, width * abi.TEXEL_BYTES.get(fmt, 4) if pitch is None else pitch, fmt)
 
 
 def refusal_cases(S=0x10000000, D=0x20000000):

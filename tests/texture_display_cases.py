@@ -9,6 +9,9 @@ SRC_EXTENT, DST_EXTENT = (64, 32), (48, 24)
 
 
 def image(width, height, fmt, address, pitch=None):
+    """An szg_image at `address`, tightly packed unless `pitch` says otherwise. The refusal lists here and in
+    tests/test_present_model.py, tests/test_compute_collection_reflection.py and tests/refusal_texts.py build theirs over
+    memory that is never touched: a refusal is decided on the host, before anything is launched."""
     return abi.Image(address, width, height, width * abi.TEXEL_BYTES.get(fmt, 4) if pitch is None else pitch, fmt)
 
 
