@@ -12,13 +12,10 @@
 //                  LDS, only for the formats that need it: an sRGB table costs 256 szg_powf per workgroup, a texel four
 //                  LDS reads and no conversion.
 //   k_image_clear  the same groups, one value.
-// Destination texels are grouped in twos by ADDRESS, not by column: group g of a row covers the 16 aligned bytes counted from
-// the 16-B boundary at or below the row's first texel, so that a full group is one aligned 16-B store whatever the region
-// offset and the pitch. The groups that straddle the region's left or right edge, and every group of a row that is not
-// 16-B aligned like row 0, fall back to one predicated 8-B store per texel: nothing outside the region is written.
-#include "szg_device.hpp"
+// Destination texels are grouped in twos by address (RowGroups<8> of szg_image_ops.hpp): a full group of a row aligned like
+// row 0 is one aligned 16-B store, every other texel one predicated 8-B store; nothing outside the region is written.
+#include "szg_image_ops.hpp"
 #include "szg_launch.hpp"
-#include "szg_texture.hpp"
 
 #include "szg/texture_display.h"
 
@@ -26,9 +23,6 @@ namespace szg
 {
 namespace
 {
-// float(code) / 65535.0f, the UNORM16 load of the library (kernels_present.hip: correctly rounded for every code)
-SZG_DEV float unorm16_to_float(unsigned code) { return divR0((float)code, 65535.0f, 0x1.0001p-16f); }
-
 // STORE of the header for one channel: binary16 of the ROUNDED fp32 value (the guard of pack_half4)
 SZG_DEV unsigned half_code(float x)
 {
@@ -37,19 +31,30 @@ SZG_DEV unsigned half_code(float x)
     return (unsigned)*reinterpret_cast<const unsigned short*>(&h);
 }
 
-// texels of a row's first group that lie in front of the region (0 or 1)
-SZG_DEV unsigned lead_texels(const unsigned char* row) { return ((unsigned)reinterpret_cast<uintptr_t>(row) & 15u) >> 3; }
+using Groups = RowGroups<8>; // 8-B destination texels
 
-SZG_DEV int axis_nearest(int k, int s0, int sw, int n, int extent)
+// The group's two texels: one 16-B store where the group is full and this row puts it on a 16-B boundary, otherwise one
+// predicated 8-B store per texel. One function body on purpose: split into the pieces of RowGroups<4>, the address of the
+// first 8-B store no longer merges with the 16-B store's (+2 VGPRs, 1.1 % to 1.5 % slower; profiles/image_ops_refactor.md).
+SZG_DEV void store_pair(unsigned char* drow, int c0, bool full, unsigned width, uint2 t0, uint2 t1)
 {
-    int const i = s0 + ((2 * k + 1) * sw) / (2 * n); // below 2^30: extents <= 16384
-    return min(max(i, 0), extent - 1);
+    unsigned char* p = drow + (ptrdiff_t)c0 * 8;
+    if (full && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u)
+    {
+        *reinterpret_cast<uint4*>(p) = make_uint4(t0.x, t0.y, t1.x, t1.y);
+    }
+    else
+    {
+        if (c0 >= 0 && (unsigned)c0 < width)
+        {
+            *reinterpret_cast<uint2*>(drow + (size_t)c0 * 8u) = t0;
+        }
+        if (c0 + 1 >= 0 && (unsigned)(c0 + 1) < width)
+        {
+            *reinterpret_cast<uint2*>(drow + (size_t)(c0 + 1) * 8u) = t1;
+        }
+    }
 }
-
-struct SrcRegion
-{
-    int x, y, width, height;
-};
 
 template <unsigned SRC> constexpr unsigned source_texel_bytes() { return SRC == SZG_FORMAT_RGBA8_UNORM || SRC == SZG_FORMAT_RGBA8_SRGB ? 4u : 8u; }
 
@@ -62,9 +67,8 @@ template <unsigned SRC> SZG_DEV uint2 convert_texel(const unsigned char* p, cons
     }
     if (SRC == SZG_FORMAT_RGBA16_UNORM)
     {
-        uint2 const t = *reinterpret_cast<const uint2*>(p);
-        return pack_half4(unorm16_to_float(t.x & 0xFFFFu), unorm16_to_float(t.x >> 16), unorm16_to_float(t.y & 0xFFFFu),
-                          unorm16_to_float(t.y >> 16));
+        V4 const t = unpack_unorm16x4(*reinterpret_cast<const uint2*>(p));
+        return pack_half4(t.x, t.y, t.z, t.w);
     }
     unsigned const t = *reinterpret_cast<const unsigned*>(p);
     return make_uint2((unsigned)colour[t & 0xFFu] | ((unsigned)colour[(t >> 8) & 0xFFu] << 16),
@@ -94,15 +98,14 @@ __global__ __launch_bounds__(256) void k_image_copy(const unsigned char* __restr
     const unsigned short* const alpha = tables + (SRGB ? 256 : 0);
 
     // groups by the alignment of row 0; a row aligned otherwise (a pitch that is no multiple of 16) takes the 8-B stores
-    unsigned const lead = lead_texels(dst);
-    unsigned const groups = (width + lead + 1u) / 2u;
+    unsigned const lead = Groups::lead_texels(dst);
     unsigned const v = blockIdx.x * 256u + threadIdx.x;
-    if (v >= groups)
+    if (v >= Groups::count(width, lead))
     {
         return;
     }
-    int const c0 = (int)(2u * v) - (int)lead; // first column of the group; < 0 only for v == 0
-    bool const full = c0 >= 0 && (unsigned)c0 + 2u <= width;
+    int const c0 = Groups::first_column(v, lead);
+    bool const full = Groups::full(c0, width);
     // per-column setup, once per lane; a column outside the region is computed but never stored
     unsigned off[2];
 #pragma unroll
@@ -118,22 +121,7 @@ __global__ __launch_bounds__(256) void k_image_copy(const unsigned char* __restr
         unsigned char* drow = dst + (size_t)y * dstPitch;
         uint2 const t0 = convert_texel<SRC>(srow + off[0], colour, alpha);
         uint2 const t1 = convert_texel<SRC>(srow + off[1], colour, alpha);
-        unsigned char* p = drow + (ptrdiff_t)c0 * 8;
-        if (full && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u)
-        {
-            *reinterpret_cast<uint4*>(p) = make_uint4(t0.x, t0.y, t1.x, t1.y);
-        }
-        else
-        {
-            if (c0 >= 0 && (unsigned)c0 < width)
-            {
-                *reinterpret_cast<uint2*>(drow + (size_t)c0 * 8u) = t0;
-            }
-            if (c0 + 1 >= 0 && (unsigned)(c0 + 1) < width)
-            {
-                *reinterpret_cast<uint2*>(drow + (size_t)(c0 + 1) * 8u) = t1;
-            }
-        }
+        store_pair(drow, c0, full, width, t0, t1);
     }
 }
 
@@ -143,42 +131,24 @@ __global__ __launch_bounds__(256) void k_image_clear(unsigned char* __restrict__
                                                      V4 color)
 {
     uint2 const t = HALF ? pack_half4(color.x, color.y, color.z, color.w) : pack_unorm16x4(color.x, color.y, color.z, color.w);
-    unsigned const lead = lead_texels(dst);
-    unsigned const groups = (width + lead + 1u) / 2u;
+    unsigned const lead = Groups::lead_texels(dst);
     unsigned const v = blockIdx.x * 256u + threadIdx.x;
-    if (v >= groups)
+    if (v >= Groups::count(width, lead))
     {
         return;
     }
-    int const c0 = (int)(2u * v) - (int)lead;
-    bool const full = c0 >= 0 && (unsigned)c0 + 2u <= width;
+    int const c0 = Groups::first_column(v, lead);
+    bool const full = Groups::full(c0, width);
     for (unsigned y = blockIdx.y; y < height; y += gridDim.y)
     {
-        unsigned char* drow = dst + (size_t)y * dstPitch;
-        unsigned char* p = drow + (ptrdiff_t)c0 * 8;
-        if (full && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u)
-        {
-            *reinterpret_cast<uint4*>(p) = make_uint4(t.x, t.y, t.x, t.y);
-        }
-        else
-        {
-            if (c0 >= 0 && (unsigned)c0 < width)
-            {
-                *reinterpret_cast<uint2*>(drow + (size_t)c0 * 8u) = t;
-            }
-            if (c0 + 1 >= 0 && (unsigned)(c0 + 1) < width)
-            {
-                *reinterpret_cast<uint2*>(drow + (size_t)(c0 + 1) * 8u) = t;
-            }
-        }
+        store_pair(dst + (size_t)y * dstPitch, c0, full, width, t, t);
     }
 }
 
 // the grid of both kernels: 256 groups per workgroup along x, IMAGE_COPY_ROWS_PER_LANE rows per lane along y
 dim3 group_grid(unsigned width, unsigned height)
 {
-    unsigned const groups = (width + 1u + 1u) / 2u; // at most 1 leading texel
-    return dim3((groups + 255u) / 256u, (height + IMAGE_COPY_ROWS_PER_LANE - 1u) / IMAGE_COPY_ROWS_PER_LANE);
+    return dim3((Groups::count(width) + 255u) / 256u, (height + IMAGE_COPY_ROWS_PER_LANE - 1u) / IMAGE_COPY_ROWS_PER_LANE);
 }
 
 template <unsigned SRC>

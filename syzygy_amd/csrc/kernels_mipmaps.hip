@@ -5,22 +5,11 @@
 //
 // One thread per destination texel: four dword loads (the texel pair of two source rows) and one dword store. A wave
 // covers 32 x 2 destination texels: it reads four contiguous 256-byte row segments and writes two of 128 bytes.
+#include "szg_image_ops.hpp"
 #include "szg_launch.hpp"
-#include "szg_texture.hpp"
 
 namespace szg
 {
-namespace
-{
-// SZG_OETF_SRGB of szg_record_oetf (kernels_deferred.hip oetf()): the same expression
-SZG_DEV float encodeSrgb(float linear)
-{
-    float const lower = 12.92f * linear;
-    float const higher = szg_powf(linear, (float)(1.0 / 2.4)) * 1.055f - 0.055f;
-    return (linear <= 0.0031308f) ? lower : higher;
-}
-} // namespace
-
 __global__ __launch_bounds__(256) void k_mip_downsample(const unsigned char* __restrict__ src, unsigned srcW, unsigned srcH,
                                                         unsigned srcPitch, unsigned char* __restrict__ dst, unsigned dstW,
                                                         unsigned dstH, unsigned srgb)
@@ -56,7 +45,7 @@ __global__ __launch_bounds__(256) void k_mip_downsample(const unsigned char* __r
         if (srgb != 0u && ch < 3u)
         {
             float const l = ((s_srgb[a] + s_srgb[b]) + (s_srgb[c] + s_srgb[e])) * 0.25f;
-            int const q = (int)floorf(encodeSrgb(l) * 255.0f + 0.5f);
+            int const q = (int)floorf(encode_srgb(l) * 255.0f + 0.5f);
             code = (unsigned)min(max(q, 0), 255);
         }
         out |= code << sh;

@@ -10,11 +10,9 @@
 //   k_present_scale  everything else. A lane owns 4 adjacent destination columns, computes their taps and weights once
 //                    and keeps them over the rows it walks; the row's taps and weight are wave-uniform. Taps are 8-B
 //                    gathers (for a magnification they hit the same lines again; a 4K source fits the Infinity Cache).
-// Destination texels are grouped in fours by ADDRESS, not by column: group g of a row covers the 16 aligned bytes
-// 16 g .. 16 g + 15 counted from the 16-B boundary at or below the row's first texel, so that a full group is one aligned
-// 16-B store whatever the region offset and the pitch. The groups that straddle the region's left or right edge fall back
-// to one predicated 4-B store per texel: nothing outside the region is read (1:1) or written.
-#include "szg_device.hpp"
+// Destination texels are grouped in fours by address (RowGroups<4> of szg_image_ops.hpp): a full group is one aligned 16-B
+// store, the groups at the region's edges store texel by texel; nothing outside the region is read (1:1) or written.
+#include "szg_image_ops.hpp"
 #include "szg_launch.hpp"
 
 #include "szg/present.h"
@@ -29,11 +27,6 @@ struct alignas(8) Quad8
 {
     unsigned x, y, z, w;
 };
-
-// float(code) / 65535.0f, the UNORM16 load of the library. RN(1 / 65535) is 0x1.0001p-16, and with it divR0 (Markstein)
-// returns the correctly rounded quotient for every one of the 65 536 codes: checked exhaustively in exact arithmetic by
-// tests/test_present_model.py and on the device by tests/test_gpu_present.py. 3 instructions instead of the ~11 of `/`.
-SZG_DEV float unorm16_to_float(unsigned code) { return divR0((float)code, 65535.0f, 0x1.0001p-16f); }
 
 // STORE of the header: clamp, scale by 2^b - 1, round to nearest even
 SZG_DEV unsigned unorm_bits(float x, float scale)
@@ -71,8 +64,7 @@ template <unsigned FMT, bool ENC> SZG_DEV unsigned convert_texel(uint2 t, const 
     return pack_texel<FMT>(load_tap<ENC>(t, table));
 }
 
-// texels of a row's first group that lie in front of the region (0..3): the row starts `lead` texels after a 16-B boundary
-SZG_DEV unsigned lead_texels(const unsigned char* row) { return ((unsigned)reinterpret_cast<uintptr_t>(row) & 15u) >> 2; }
+using Groups = RowGroups<4>; // 4-B destination texels
 
 // `src` / `dst` point at the first texel of the regions
 template <unsigned FMT, bool ENC>
@@ -84,12 +76,12 @@ __global__ __launch_bounds__(256) void k_present_copy(const unsigned char* __res
     {
         const unsigned char* srow = src + (size_t)y * srcPitch;
         unsigned char* drow = dst + (size_t)y * dstPitch;
-        unsigned const lead = lead_texels(drow);
-        unsigned const groups = (width + lead + 3u) / 4u;
+        unsigned const lead = Groups::lead_texels(drow); // of this row: its full groups are aligned whatever the pitch
+        unsigned const groups = Groups::count(width, lead);
         for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < groups; v += gridDim.x * 256u)
         {
-            int const c0 = (int)(4u * v) - (int)lead; // first column of the group; < 0 only for v == 0
-            if (c0 >= 0 && (unsigned)c0 + 4u <= width)
+            int const c0 = Groups::first_column(v, lead);
+            if (Groups::full(c0, width))
             {
                 const Quad8* s = reinterpret_cast<const Quad8*>(srow + (size_t)c0 * 8u);
                 Quad8 const p01 = s[0];
@@ -99,7 +91,7 @@ __global__ __launch_bounds__(256) void k_present_copy(const unsigned char* __res
                 out.y = convert_texel<FMT, ENC>(make_uint2(p01.z, p01.w), table);
                 out.z = convert_texel<FMT, ENC>(make_uint2(p23.x, p23.y), table);
                 out.w = convert_texel<FMT, ENC>(make_uint2(p23.z, p23.w), table);
-                *reinterpret_cast<uint4*>(drow + (size_t)c0 * 4u) = out; // 16-B aligned by construction of the groups
+                Groups::store_aligned(Groups::address(drow, c0), out); // 16-B aligned: `lead` is this row's
             }
             else
             {
@@ -107,44 +99,16 @@ __global__ __launch_bounds__(256) void k_present_copy(const unsigned char* __res
                 for (int i = 0; i < 4; i++)
                 {
                     int const c = c0 + i;
-                    if (c >= 0 && (unsigned)c < width)
+                    if (Groups::holds(c, width)) // nothing outside the region is read either
                     {
                         uint2 const t = *reinterpret_cast<const uint2*>(srow + (size_t)c * 8u);
-                        *reinterpret_cast<unsigned*>(drow + (size_t)c * 4u) = convert_texel<FMT, ENC>(t, table);
+                        Groups::store_texel(drow, c, width, convert_texel<FMT, ENC>(t, table));
                     }
                 }
             }
         }
     }
 }
-
-// COORDINATES of the header for one axis: destination index k of n onto source texels [s0, s0 + sw) of an image of
-// `extent` texels. All products stay below 2^30 (extents <= 16384).
-SZG_DEV void axis_linear(int k, int s0, int sw, int n, int extent, int& i0, int& i1, float& alpha)
-{
-    int const num = (2 * k + 1) * sw + (2 * s0 - 1) * n;
-    int const den = 2 * n;
-    int q = num / den; // truncates; num >= -n, so only q == 0 with a negative remainder needs the floor fix
-    int rem = num - q * den;
-    if (rem < 0)
-    {
-        rem += den;
-        q -= 1;
-    }
-    alpha = (float)rem / (float)den;
-    i0 = min(max(q, 0), extent - 1);
-    i1 = min(max(q + 1, 0), extent - 1);
-}
-SZG_DEV int axis_nearest(int k, int s0, int sw, int n, int extent)
-{
-    int const i = s0 + ((2 * k + 1) * sw) / (2 * n);
-    return min(max(i, 0), extent - 1);
-}
-
-struct SrcRegion
-{
-    int x, y, width, height;
-};
 
 // `src` points at texel (0, 0) of the source IMAGE (taps may leave the region), `dst` at the first texel of the region
 template <unsigned FMT, bool ENC, bool LINEAR>
@@ -154,15 +118,13 @@ __global__ __launch_bounds__(256) void k_present_scale(const unsigned char* __re
 {
     // groups by the alignment of row 0; with a pitch that is a multiple of 16 every row has the same one, otherwise the
     // rows that do not take the per-texel stores below
-    unsigned const lead = lead_texels(dst);
-    unsigned const groups = (width + lead + 3u) / 4u;
+    unsigned const lead = Groups::lead_texels(dst);
     unsigned const v = blockIdx.x * 256u + threadIdx.x;
-    if (v >= groups)
+    if (v >= Groups::count(width, lead))
     {
         return;
     }
-    int const c0 = (int)(4u * v) - (int)lead;
-    bool const full = c0 >= 0 && (unsigned)c0 + 4u <= width;
+    int const c0 = Groups::first_column(v, lead);
     // per-column setup, once per lane: byte offsets of the two taps, the weight and its complement
     unsigned off0[4], off1[4];
     float alpha[4], oneMinusAlpha[4];
@@ -205,12 +167,9 @@ __global__ __launch_bounds__(256) void k_present_scale(const unsigned char* __re
                 V4 const t10 = load_tap<ENC>(*reinterpret_cast<const uint2*>(r0 + off1[i]), table);
                 V4 const t01 = load_tap<ENC>(*reinterpret_cast<const uint2*>(r1 + off0[i]), table);
                 V4 const t11 = load_tap<ENC>(*reinterpret_cast<const uint2*>(r1 + off1[i]), table);
-                float const a = alpha[i], na = oneMinusAlpha[i];
-                V4 const top{t00.x * na + t10.x * a, t00.y * na + t10.y * a, t00.z * na + t10.z * a, t00.w * na + t10.w * a};
-                V4 const bot{t01.x * na + t11.x * a, t01.y * na + t11.y * a, t01.z * na + t11.z * a, t01.w * na + t11.w * a};
-                V4 const r{top.x * oneMinusBeta + bot.x * beta, top.y * oneMinusBeta + bot.y * beta,
-                           top.z * oneMinusBeta + bot.z * beta, top.w * oneMinusBeta + bot.w * beta};
-                out[i] = pack_texel<FMT>(r);
+                V4 const top = blend(t00, t10, oneMinusAlpha[i], alpha[i]);
+                V4 const bot = blend(t01, t11, oneMinusAlpha[i], alpha[i]);
+                out[i] = pack_texel<FMT>(blend(top, bot, oneMinusBeta, beta));
             }
         }
         else
@@ -223,23 +182,7 @@ __global__ __launch_bounds__(256) void k_present_scale(const unsigned char* __re
                 out[i] = convert_texel<FMT, ENC>(*reinterpret_cast<const uint2*>(r0 + off0[i]), table);
             }
         }
-        unsigned char* p = drow + (ptrdiff_t)c0 * 4;
-        if (full && (reinterpret_cast<uintptr_t>(p) & 15u) == 0u)
-        {
-            *reinterpret_cast<uint4*>(p) = make_uint4(out[0], out[1], out[2], out[3]);
-        }
-        else
-        {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-            {
-                int const c = c0 + i;
-                if (c >= 0 && (unsigned)c < width)
-                {
-                    *reinterpret_cast<unsigned*>(drow + (size_t)c * 4u) = out[i];
-                }
-            }
-        }
+        Groups::store(drow, c0, width, make_uint4(out[0], out[1], out[2], out[3]));
     }
 }
 
@@ -250,8 +193,7 @@ hipError_t launch_present_fmt(hipStream_t s, const szg_image& src, const szg_ima
     szg_rect const& sr = info.src_region;
     szg_rect const& dr = info.dst_region;
     unsigned char* dstRegion = static_cast<unsigned char*>(dst.data) + (size_t)dr.y * dst.pitch_bytes + (size_t)dr.x * 4u;
-    unsigned const groups = (dr.width + 3u + 3u) / 4u; // at most 3 leading texels
-    unsigned const gx = (groups + 255u) / 256u;
+    unsigned const gx = (Groups::count(dr.width) + 255u) / 256u;
     if (sr.width == dr.width && sr.height == dr.height)
     {
         const unsigned char* srcRegion = static_cast<const unsigned char*>(src.data) + (size_t)sr.y * src.pitch_bytes + (size_t)sr.x * 8u;
@@ -284,7 +226,7 @@ hipError_t launch_present_enc(hipStream_t s, const szg_image& src, const szg_ima
 }
 } // namespace
 
-// Arguments are validated by szg_record_present (szg_api.cpp); `table` is the OETF table of info.encode or NULL for
+// Arguments are validated by szg_record_present (api_image_passes.cpp); `table` is the OETF table of info.encode or NULL for
 // SZG_PRESENT_ENCODE_NONE.
 hipError_t launch_present(hipStream_t s, const szg_image& src, const szg_image& dst, const szg_present_info& info,
                           const unsigned short* table)

@@ -19,7 +19,7 @@
 //                Per pixel the edge values are the patch origin's (scalar 64-bit arithmetic) plus lane multiples below 8 of the
 //                steps; the 64 x 64-bit products stay out of the lanes.
 // UI geometry is spatially coherent in submission order (a window, then its widgets), which keeps the union boxes tight.
-#include "szg_device.hpp"
+#include "szg_image_ops.hpp"
 #include "szg_launch.hpp"
 
 #include "szg/texture_display.h"
@@ -124,10 +124,10 @@ __global__ __launch_bounds__(64) void k_ui_setup(UIDrawParams d, const UICommand
                     }
                     p.u[i] = vtx[i].uv[0];
                     p.v[i] = vtx[i].uv[1];
-                    p.r[i] = (float)(vtx[i].col & 0xFFu) / 255.0f;
-                    p.g[i] = (float)((vtx[i].col >> 8) & 0xFFu) / 255.0f;
-                    p.b[i] = (float)((vtx[i].col >> 16) & 0xFFu) / 255.0f;
-                    p.a[i] = (float)(vtx[i].col >> 24) / 255.0f;
+                    p.r[i] = decode8(vtx[i].col & 0xFFu, false);
+                    p.g[i] = decode8((vtx[i].col >> 8) & 0xFFu, false);
+                    p.b[i] = decode8((vtx[i].col >> 16) & 0xFFu, false);
+                    p.a[i] = decode8(vtx[i].col >> 24, false);
                 }
                 p.det = (float)(det > 0 ? det : -det);
                 p.topLeft = topLeft;
@@ -166,10 +166,6 @@ __global__ __launch_bounds__(64) void k_ui_super(const uint2* __restrict__ chunk
         superBoxes[blockIdx.x] = u;
     }
 }
-
-// float(code) / 65535.0f. RN(1 / 65535) is 0x1.0001p-16, and with it divR0 returns the correctly rounded quotient for every
-// one of the 65 536 codes (kernels_present.hip; here tests/test_gpu_ui_layer.py runs every code through both uses).
-SZG_DEV float unorm16ToFloat(unsigned code) { return divR0((float)code, 65535.0f, 0x1.0001p-16f); }
 
 // REPEAT of the header: wrapIndex of szg_texture.hpp without its out-of-range conversion
 SZG_DEV int repeatIndex(float f, float fn)
@@ -233,11 +229,10 @@ SZG_DEV V4 fetchTexel(const UICommand& c, int i, int j, bool outside)
         {
             return unpack_half4(t); // exact: denormals kept, inf and NaN as they are
         }
-        return V4{unorm16ToFloat(t.x & 0xFFFFu), unorm16ToFloat(t.x >> 16), unorm16ToFloat(t.y & 0xFFFFu), unorm16ToFloat(t.y >> 16)};
+        return unpack_unorm16x4(t);
     }
     unsigned const t = *reinterpret_cast<const unsigned*>(row + (size_t)i * 4u);
-    return V4{(float)(t & 0xFFu) / 255.0f, (float)((t >> 8) & 0xFFu) / 255.0f, (float)((t >> 16) & 0xFFu) / 255.0f,
-              (float)(t >> 24) / 255.0f};
+    return V4{decode8(t & 0xFFu, false), decode8((t >> 8) & 0xFFu, false), decode8((t >> 16) & 0xFFu, false), decode8(t >> 24, false)};
 }
 
 // MAPPING of szg/texture_display.h for one channel of the filtered sample: `s` is a VkComponentSwizzle, `own` the channel's
@@ -281,10 +276,8 @@ SZG_DEV V4 filteredSample(const UICommand& c, float u, float v)
     V4 const t10 = fetchTexel(c, tx.i1, ty.i0, tx.out1 || ty.out0);
     V4 const t01 = fetchTexel(c, tx.i0, ty.i1, tx.out0 || ty.out1);
     V4 const t11 = fetchTexel(c, tx.i1, ty.i1, tx.out1 || ty.out1);
-    float const a = tx.w, na = 1.0f - a, b = ty.w, nb = 1.0f - b;
-    V4 const top{t00.x * na + t10.x * a, t00.y * na + t10.y * a, t00.z * na + t10.z * a, t00.w * na + t10.w * a};
-    V4 const bot{t01.x * na + t11.x * a, t01.y * na + t11.y * a, t01.z * na + t11.z * a, t01.w * na + t11.w * a};
-    return V4{top.x * nb + bot.x * b, top.y * nb + bot.y * b, top.z * nb + bot.z * b, top.w * nb + bot.w * b};
+    float const na = 1.0f - tx.w, nb = 1.0f - ty.w;
+    return blend(blend(t00, t10, na, tx.w), blend(t01, t11, na, tx.w), nb, ty.w);
 }
 
 SZG_DEV float saturate01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); } // NaN -> 0
@@ -366,10 +359,9 @@ __global__ __launch_bounds__(256) void k_ui_tile(unsigned char* __restrict__ out
                     V4 const tex = sampleUI(commands[p.command], u, v);
                     float const fr = saturate01(cr * tex.x), fg = saturate01(cg * tex.y), fb = saturate01(cb * tex.z);
                     float const fa = saturate01(ca * tex.w);
-                    float const dr = unorm16ToFloat(dst.x & 0xFFFFu), dg = unorm16ToFloat(dst.x >> 16);
-                    float const db = unorm16ToFloat(dst.y & 0xFFFFu), da = unorm16ToFloat(dst.y >> 16);
+                    V4 const d = unpack_unorm16x4(dst);
                     float const na = 1.0f - fa;
-                    dst = pack_unorm16x4(fr * fa + dr * na, fg * fa + dg * na, fb * fa + db * na, fa + da * na);
+                    dst = pack_unorm16x4(fr * fa + d.x * na, fg * fa + d.y * na, fb * fa + d.z * na, fa + d.w * na);
                 }
             }
         }

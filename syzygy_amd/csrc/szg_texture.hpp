@@ -1,6 +1,6 @@
 // szg_texture.hpp — the material sampler of the G-buffer raster pass as device functions, shared by k_raster_tile
-// (kernels_raster.hip), k_mip_downsample (kernels_mipmaps.hip: decode8) and the sampler test kernel
-// (tests/mipsample/mipsample.hip). The rules are those of include/szg/raster.h "textures" (one level) and
+// (kernels_raster.hip), the image passes through szg_image_ops.hpp (decode8: the mip builder, the image copy, the UI layer)
+// and the sampler test kernel (tests/mipsample/mipsample.hip). The rules are those of include/szg/raster.h "textures" (one level) and
 // include/szg/mipmaps.h "SAMPLER" (a registered chain); every translation unit that includes this is built with
 // -ffp-contract=off, so each operation below rounds once.
 #ifndef SZG_TEXTURE_HPP
