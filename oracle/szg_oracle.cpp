@@ -385,13 +385,13 @@ inline vec3 sample_linear_rgb(const Image& im, vec2 st)
     float const fv = floorf(v);
     float const a = u - fu;
     float const b = v - fv;
-    int i0 = (int)fu, j0 = (int)fv;
-    int i1 = i0 + 1, j1 = j0 + 1;
+    // CLAMP_TO_EDGE of the two texel indices, clamped in float so that the int cast is defined: a coordinate beyond the
+    // range of int (a transmittance-LUT row for a radius of 2^30 Mm is 4e10) reads the LAST texel, where the plain cast -
+    // undefined there, INT_MIN on x86 - read the first. A NaN coordinate has NaN weights whichever texels it reads: index 0.
     int const W = (int)im.width, H = (int)im.height;
-    i0 = std::min(std::max(i0, 0), W - 1);
-    i1 = std::min(std::max(i1, 0), W - 1);
-    j0 = std::min(std::max(j0, 0), H - 1);
-    j1 = std::min(std::max(j1, 0), H - 1);
+    auto const edge = [](float f, int n) { return !(f > 0.0f) ? 0 : (f >= (float)(n - 1) ? n - 1 : (int)f); };
+    int const i0 = edge(fu, W), i1 = edge(fu + 1.0f, W);
+    int const j0 = edge(fv, H), j1 = edge(fv + 1.0f, H);
     vec4 const t00 = texel_rgba32f(im, i0, j0);
     vec4 const t10 = texel_rgba32f(im, i1, j0);
     vec4 const t01 = texel_rgba32f(im, i0, j1);
