@@ -68,6 +68,8 @@ def main(argv=None):
     ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
                     help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
                          "(default), reference (the reference sampler's 1.0) or a number")
+    ap.add_argument("--anisotropy", default=None, metavar="A",
+                    help="with --mipmaps: the sampler's maxAnisotropy, 1 to 16 (szg/anisotropy.h); default off (1, the reference's)")
     ap.add_argument("--ui-layer", action="store_true",
                     help="draw an editor-like UI frame over the scene (szg/ui_layer.h) and present the UI output texture")
     ap.add_argument("--texture-viewer", nargs="?", const="color", default=None, choices=["color", "normal", "orm", "gbuffer-normal"],
@@ -89,6 +91,12 @@ def main(argv=None):
         max_lod = pl.parse_mipmaps_option(args.mipmaps) if args.mipmaps is not None else None
     except ValueError as e:
         ap.error(f"--mipmaps {e}")
+    try:
+        max_anisotropy = pl.parse_anisotropy_option(args.anisotropy) if args.anisotropy is not None else 1.0
+    except ValueError as e:
+        ap.error(f"--anisotropy {e}")
+    if args.anisotropy is not None and max_lod is None:
+        ap.error("--anisotropy needs --mipmaps: only maps with a mip chain are filtered anisotropically")
     # ---- scene: the editor's start-up scene, its cubes animated (editor.cpp:500-545) -----------------------------
     material = meshes.default_material()
     cv, ci = meshes.cube_mesh()
@@ -186,7 +194,7 @@ def main(argv=None):
             collection.recordDrawCommands(None, target, rect)
         else:
             if max_lod is not None:  # the meshes of a frame are new uploads: their chains are registered with them
-                meshes.register_texture_mips(deferred, scene_meshes, max_lod)
+                meshes.register_texture_mips(deferred, scene_meshes, max_lod, max_anisotropy=max_anisotropy)
             deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
             sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
             debug_lines.pushBox(tuple(bounds.center), (0.0, 0.0, 0.0, 1.0), tuple(bounds.half_extent))  # renderer.cpp:417-423

@@ -65,6 +65,8 @@ def main(argv=None):
     ap.add_argument("--mipmaps", nargs="?", const="none", default=None, metavar="MAXLOD",
                     help="build mip chains for the material textures and sample them trilinearly (szg/mipmaps.h); MAXLOD: none "
                          "(default), reference (the reference sampler's 1.0) or a number")
+    ap.add_argument("--anisotropy", default=None, metavar="A",
+                    help="with --mipmaps: the sampler's maxAnisotropy, 1 to 16 (szg/anisotropy.h); default off (1, the reference's)")
     ap.add_argument("--jpeg", nargs="?", const="host", default=None, choices=("host", "device"), metavar="host|device",
                     help="decode JPEG material maps (szg/jpeg.h; default: PNG only, as before): on the host, or the entropy decode on "
                          "the host and IDCT, upsampling and colour conversion on the GPU")
@@ -82,6 +84,12 @@ def main(argv=None):
         max_lod = pl.parse_mipmaps_option(args.mipmaps) if args.mipmaps is not None else None
     except ValueError as e:
         ap.error(f"--mipmaps {e}")
+    try:
+        max_anisotropy = pl.parse_anisotropy_option(args.anisotropy) if args.anisotropy is not None else 1.0
+    except ValueError as e:
+        ap.error(f"--anisotropy {e}")
+    if args.anisotropy is not None and max_lod is None:
+        ap.error("--anisotropy needs --mipmaps: only maps with a mip chain are filtered anisotropically")
 
     path = args.path
     if not path:
@@ -150,7 +158,8 @@ def main(argv=None):
         if max_lod is not None:
             for m in scene_meshes:
                 m.mipmaps = True  # chains are built with the upload, or now for a mesh that is already on the device
-            print(f"mip chains for {meshes.register_texture_mips(deferred, scene_meshes, max_lod)} textures, max_lod {max_lod:g}")
+            count = meshes.register_texture_mips(deferred, scene_meshes, max_lod, max_anisotropy=max_anisotropy)
+            print(f"mip chains for {count} textures, max_lod {max_lod:g}, max_anisotropy {max_anisotropy:g}")
         deferred.recordDrawCommandsMeshes(None, rect, target, 1, lights, spots, 0, cameras, scene_meshes)
         sky.recordDrawCommands(None, target, rect, deferred.gbuffer(), deferred.shadowMaps(), 0, atmospheres, 0, cameras, 0, lights)
     pl.recordOETF(None, target, W, H)

@@ -47,7 +47,8 @@
  *               bilinear(level k) is the one-level rule of szg/raster.h "textures" with w_k, h_k. No LOD bias, no
  *               anisotropy (vulkanstructs.cpp:147-183). A magnified pixel (lam == 0), a texture without a table entry
  *               and an entry with level_count == 1 give the one-level value bit for bit. A pipeline without a table
- *               launches the kernel it launched before this header existed.
+ *               launches the kernel it launched before this header existed. (Anisotropy is opt-in sampler state of its own:
+ *               szg/anisotropy.h; at its default this rule is all there is.)
  *
  * The table is keyed by the level-0 DEVICE POINTER, which plays the role the image handle plays in Vulkan: width, height
  * and srgb still come from the surface's szg_texture. The shadow raster reads no texture and is untouched.

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/anisotropy.h"
 #include "szg/compute_collection.h"
 #include "szg/debuglines.h"
 #include "szg/mipmaps.h"
@@ -339,6 +340,12 @@ struct DeferredShadingPipeline
     {
         return detail::note(szg_deferred_set_texture_mips(m_handle, entries.data(), static_cast<uint32_t>(entries.size()), maxLod),
                             "szg_deferred_set_texture_mips", m_lastStatus);
+    }
+    // szg/anisotropy.h: the sampler's maxAnisotropy, SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE (1.0, the reference's:
+    // vulkanstructs.cpp:171-172) to SZG_SAMPLER_MAX_ANISOTROPY_LIMIT; it applies to the maps that have a chain.
+    auto setSamplerAnisotropy(float maxAnisotropy) -> int
+    {
+        return detail::note(szg_deferred_set_sampler_anisotropy(m_handle, maxAnisotropy), "szg_deferred_set_sampler_anisotropy", m_lastStatus);
     }
     [[nodiscard]] auto valid() const -> bool { return m_handle != nullptr; }
 

@@ -611,6 +611,13 @@ MIPMAP_FUNCTIONS = {
     "szg_deferred_set_texture_mips": (C.c_int, [VP, P(TextureMips), U32, C.c_float]),
 }
 
+# include/szg/anisotropy.h
+SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE = 1.0
+SZG_SAMPLER_MAX_ANISOTROPY_LIMIT = 16.0
+ANISOTROPY_FUNCTIONS = {
+    "szg_deferred_set_sampler_anisotropy": (C.c_int, [VP, C.c_float]),
+}
+
 # include/szg/ui_layer.h
 SZG_UI_ADDRESS_REPEAT = 0
 SZG_UI_ADDRESS_CLAMP_TO_EDGE = 2
@@ -732,6 +739,7 @@ BINDINGS = [
     ("jpeg.h", JPEG_FUNCTIONS, "JPEG material maps are unavailable with it"),
     ("texture_display.h", TEXTURE_DISPLAY_FUNCTIONS, "the texture viewer is unavailable with it"),
     ("light_tiles.h", LIGHT_TILE_FUNCTIONS, "the light tile masks cannot be read back with it"),
+    ("anisotropy.h", ANISOTROPY_FUNCTIONS, "anisotropic filtering is unavailable with it"),
 ]
 
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "szg/abi.h"
+#include "szg/anisotropy.h"
 #include "szg/mipmaps.h"
 #include "szg_internal.hpp"
 #include "szg_launch.hpp"
@@ -258,6 +259,8 @@ struct szg_deferred
     // szg/mipmaps.h: the table of szg_deferred_set_texture_mips, looked up by level-0 pointer at record time
     std::vector<szg_texture_mips> textureMips;
     float textureMaxLod = SZG_SAMPLER_MAX_LOD_NONE;
+    // szg/anisotropy.h: szg_deferred_set_sampler_anisotropy; above 1 the draws with a chain go to k_raster_tile_aniso
+    float textureMaxAnisotropy = SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE;
 };
 
 namespace szg

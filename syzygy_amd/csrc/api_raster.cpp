@@ -1,4 +1,5 @@
-// api_raster.cpp — the mesh passes of the deferred pipeline (szg/raster.h) and the mip chains they sample (szg/mipmaps.h).
+// api_raster.cpp — the mesh passes of the deferred pipeline (szg/raster.h), the mip chains they sample (szg/mipmaps.h) and the
+// sampler's anisotropy (szg/anisotropy.h).
 
 #include <algorithm>
 #include <functional>
@@ -67,6 +68,7 @@ int collect_draws(const char* who, const szg_mesh_instanced* meshes, uint32_t me
                 }
             }
             d.maxLod = 0.0f;
+            d.maxAnisotropy = mips != nullptr ? mips->textureMaxAnisotropy : SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE;
             for (int t = 0; t < 3; t++)
             {
                 d.mipChain[t] = nullptr;
@@ -208,7 +210,9 @@ int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect
     }
     std::vector<szg::RasterDraw> draws;
     uint32_t primCount = 0;
-    bool anyMips = false; // k_raster_tile<true> only when some draw of this call has a chain (szg/mipmaps.h)
+    // k_raster_tile<true> only when some draw of this call has a chain (szg/mipmaps.h); k_raster_tile_aniso only when, on top of
+    // that, the pipeline's maxAnisotropy is above 1 (szg/anisotropy.h)
+    bool anyMips = false;
     SZG_TRY_RC(collect_draws("szg_deferred_record_gbuffer_raster", meshes, mesh_count, false, draws, primCount, p, &anyMips));
     hipStream_t const s = static_cast<hipStream_t>(stream);
     SZG_TRY_RC(ensure_raster_capacity(p, s, draws.size(), primCount));
@@ -216,7 +220,8 @@ int szg_deferred_record_gbuffer_raster(szg_deferred_t* p, void* stream, szg_rect
     SZG_HIP(szg::launch_raster_setup(s, false, p->d_rasterDraws, (unsigned)draws.size(), primCount, d_cameras, view_camera_index, nullptr,
                                      draw_rect.width, draw_rect.height, p->raster));
     SZG_HIP(szg::launch_raster_tile(s, *scene_texture, draw_rect.width, draw_rect.height, t, p->gbuffer, p->d_rasterDraws, p->raster,
-                                    primCount, d_cameras, view_camera_index, anyMips));
+                                    primCount, d_cameras, view_camera_index, anyMips,
+                                    p->textureMaxAnisotropy > SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE));
     return SZG_OK;
 }
 
@@ -333,6 +338,28 @@ int szg_deferred_set_texture_mips(szg_deferred_t* p, const szg_texture_mips* ent
     std::sort(p->textureMips.begin(), p->textureMips.end(),
               [](szg_texture_mips const& a, szg_texture_mips const& b) { return std::less<const void*>()(a.level0_data, b.level0_data); });
     p->textureMaxLod = max_lod;
+    return SZG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Anisotropic filtering (szg/anisotropy.h)
+// ---------------------------------------------------------------------------
+int szg_deferred_set_sampler_anisotropy(szg_deferred_t* p, float max_anisotropy)
+{
+    // the argument first, the pipeline last, as szg_deferred_set_texture_mips
+    if (max_anisotropy != max_anisotropy)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_sampler_anisotropy: max_anisotropy is NaN");
+    }
+    if (max_anisotropy < SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE || max_anisotropy > SZG_SAMPLER_MAX_ANISOTROPY_LIMIT)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_sampler_anisotropy: max_anisotropy %g outside 1..16", (double)max_anisotropy);
+    }
+    if (p == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_deferred_set_sampler_anisotropy: NULL pipeline");
+    }
+    p->textureMaxAnisotropy = max_anisotropy;
     return SZG_OK;
 }
 

@@ -498,14 +498,21 @@ SZG_DEV V3 perturbNormal(V3 map, V3 N, V3 dPosDx, V3 dPosDy, V2 dUvDx, V2 dUvDy)
 } // namespace
 
 // ---------------------------------------------------------------------------
-// MIPS = false: every map is sampled at level 0 (raster.h "textures"), the kernel of a pipeline without a mip table.
-// MIPS = true: each map goes through the trilinear sampler of mipmaps.h with the chain its draw carries.
-template <bool MIPS>
-__global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image gDiffuse, szg_image gSpecular, szg_image gNormal,
-                                                     szg_image gPosition, szg_image gOrm, unsigned drawW, unsigned drawH,
-                                                     unsigned localRows, RowMap rm, const RasterDraw* __restrict__ draws,
-                                                     const PrimRec* __restrict__ prims, Hierarchy hier,
-                                                     const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex)
+// The G-buffer pass of one 32 x 8 pixel block, one 8 x 8 patch per wave. SAMPLER selects how the three maps are read:
+// SAMPLE_ONE_LEVEL: every map at level 0 (raster.h "textures"), the kernel of a pipeline without a mip table.
+// SAMPLE_MIPS: each map through the trilinear sampler of mipmaps.h with the chain its draw carries.
+// SAMPLE_ANISO: each map through the anisotropic sampler of anisotropy.h (a pipeline whose maxAnisotropy is above 1).
+enum RasterSampler
+{
+    SAMPLE_ONE_LEVEL,
+    SAMPLE_MIPS,
+    SAMPLE_ANISO
+};
+template <RasterSampler SAMPLER>
+SZG_DEV void rasterTile(szg_image depth, szg_image gDiffuse, szg_image gSpecular, szg_image gNormal, szg_image gPosition,
+                        szg_image gOrm, unsigned drawW, unsigned drawH, unsigned localRows, RowMap rm,
+                        const RasterDraw* __restrict__ draws, const PrimRec* __restrict__ prims, Hierarchy hier,
+                        const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex)
 {
     unsigned const tid = threadIdx.x;
     // RGBA8 decode tables (one entry per thread, both by the expression of decode8)
@@ -574,8 +581,14 @@ __global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image 
         Varyings const yt = isTop ? in : oy, yb = isTop ? oy : in;
         V2 const dUvDx{xr.uv.x - xl.uv.x, xr.uv.y - xl.uv.y}, dUvDy{yb.uv.x - yt.uv.x, yb.uv.y - yt.uv.y};
         auto const sample = [&](int m) {
-            return MIPS ? sampleTextureMips(d.tex[m], TextureMips{d.mipChain[m], d.mipLevels[m], d.maxLod}, in.uv, dUvDx, dUvDy, s_unorm, s_srgb)
-                        : sampleTexture(d.tex[m], in.uv, s_unorm, s_srgb);
+            if constexpr (SAMPLER == SAMPLE_ANISO)
+            {
+                return sampleTextureAniso(d.tex[m], TextureMips{d.mipChain[m], d.mipLevels[m], d.maxLod}, d.maxAnisotropy, in.uv, dUvDx,
+                                          dUvDy, s_unorm, s_srgb);
+            }
+            return SAMPLER == SAMPLE_MIPS
+                       ? sampleTextureMips(d.tex[m], TextureMips{d.mipChain[m], d.mipLevels[m], d.maxLod}, in.uv, dUvDx, dUvDy, s_unorm, s_srgb)
+                       : sampleTexture(d.tex[m], in.uv, s_unorm, s_srgb);
         };
         V3 const N = perturbNormal(sample(1), in.normal, xr.world - xl.world, yb.world - yt.world, dUvDx, dUvDy);
         V3 const color = sample(0);
@@ -591,6 +604,29 @@ __global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image 
     row_ptr<uint2>(gOrm, y)[x] = orm;
     row_ptr<float4>(gPosition, y)[x] = pos4;
     row_ptr<float>(depth, y)[x] = best;
+}
+
+template <bool MIPS>
+__global__ __launch_bounds__(256) void k_raster_tile(szg_image depth, szg_image gDiffuse, szg_image gSpecular, szg_image gNormal,
+                                                     szg_image gPosition, szg_image gOrm, unsigned drawW, unsigned drawH,
+                                                     unsigned localRows, RowMap rm, const RasterDraw* __restrict__ draws,
+                                                     const PrimRec* __restrict__ prims, Hierarchy hier,
+                                                     const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex)
+{
+    rasterTile<MIPS ? SAMPLE_MIPS : SAMPLE_ONE_LEVEL>(depth, gDiffuse, gSpecular, gNormal, gPosition, gOrm, drawW, drawH, localRows, rm,
+                                                      draws, prims, hier, cameras, cameraIndex);
+}
+
+// The third instantiation, under a name of its own so that the two above keep theirs: launched only when the pipeline's
+// maxAnisotropy is above 1 and some draw of the call carries a chain (launch_raster_tile).
+__global__ __launch_bounds__(256) void k_raster_tile_aniso(szg_image depth, szg_image gDiffuse, szg_image gSpecular, szg_image gNormal,
+                                                           szg_image gPosition, szg_image gOrm, unsigned drawW, unsigned drawH,
+                                                           unsigned localRows, RowMap rm, const RasterDraw* __restrict__ draws,
+                                                           const PrimRec* __restrict__ prims, Hierarchy hier,
+                                                           const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex)
+{
+    rasterTile<SAMPLE_ANISO>(depth, gDiffuse, gSpecular, gNormal, gPosition, gOrm, drawW, drawH, localRows, rm, draws, prims, hier, cameras,
+                             cameraIndex);
 }
 
 // ---------------------------------------------------------------------------
@@ -701,7 +737,7 @@ hipError_t launch_raster_setup(hipStream_t s, bool shadow, const RasterDraw* d_d
 
 hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                               const szg_gbuffer& g, const RasterDraw* d_draws, const RasterBuffers& b, unsigned primCount,
-                              const szg_camera_packed* d_cam, unsigned camIndex, bool mips)
+                              const szg_camera_packed* d_cam, unsigned camIndex, bool mips, bool aniso)
 {
     unsigned const rows = tile.nranks <= 1u ? drawH : tile.local_rows;
     if (rows == 0u || drawW == 0u)
@@ -710,7 +746,12 @@ hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, uns
     }
     dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
     RowMap const rm{tile.block_rows, tile.rank, tile.nranks};
-    if (mips)
+    if (mips && aniso)
+    {
+        hipLaunchKernelGGL(k_raster_tile_aniso, grid, dim3(256), 0, s, scene.depth, g.diffuse, g.specular, g.normal, g.worldPosition,
+                           g.occlusionRoughnessMetallic, drawW, drawH, rows, rm, d_draws, b.prims, hierarchyOf(b, primCount), d_cam, camIndex);
+    }
+    else if (mips)
     {
         hipLaunchKernelGGL(k_raster_tile<true>, grid, dim3(256), 0, s, scene.depth, g.diffuse, g.specular, g.normal, g.worldPosition,
                            g.occlusionRoughnessMetallic, drawW, drawH, rows, rm, d_draws, b.prims, hierarchyOf(b, primCount), d_cam, camIndex);

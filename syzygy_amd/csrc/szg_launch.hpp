@@ -141,9 +141,9 @@ hipError_t launch_shadow_prep(hipStream_t s, const szg_directional_light_packed*
 
 // ---- compute rasteriser (kernels_raster.hip, include/szg/raster.h) ----
 // One vkCmdDrawIndexed of the reference (one surface of one mesh, all its instances), uploaded by the host.
-// alignas(128) pads the 168 bytes of fields to sizeof == 256, a power of two (128 B before the mip fields), so that indexing
+// alignas(128) pads the 172 bytes of fields to sizeof == 256, a power of two (128 B before the mip fields), so that indexing
 // the record remains a shift and k_raster_tile<false> keeps the register figures it had. Records are
-// value-initialised on the host (collect_draws), so the 88 bytes of tail padding that are uploaded per draw are zeros.
+// value-initialised on the host (collect_draws), so the 84 bytes of tail padding that are uploaded per draw are zeros.
 struct alignas(128) RasterDraw
 {
     const szg_vertex_packed* vertices;
@@ -158,6 +158,8 @@ struct alignas(128) RasterDraw
     const void* mipChain[3];
     uint32_t mipLevels[3];
     float maxLod;
+    // szg/anisotropy.h: the sampler's maxAnisotropy (1..16); read by k_raster_tile_aniso only
+    float maxAnisotropy;
 };
 static_assert(sizeof(RasterDraw) == 256, "RasterDraw layout");
 // One assembled primitive: signed homogeneous edge functions + clip z, w per vertex (raster.h "coverage", "depth").
@@ -199,7 +201,7 @@ hipError_t launch_raster_setup(hipStream_t s, bool shadow, const RasterDraw* d_d
                                RasterBuffers& b);
 hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                               const szg_gbuffer& g, const RasterDraw* d_draws, const RasterBuffers& b, unsigned primCount,
-                              const szg_camera_packed* d_cam, unsigned camIndex, bool mips);
+                              const szg_camera_packed* d_cam, unsigned camIndex, bool mips, bool aniso);
 // ---- mip chains (kernels_mipmaps.hip, include/szg/mipmaps.h): arguments already validated ----
 hipError_t launch_generate_mipmaps(hipStream_t s, const szg_texture& level0, void* d_chain);
 hipError_t launch_shadow_tile(hipStream_t s, const ShadowGen* d_gen, unsigned dim, const RasterBuffers& b, unsigned primCount,

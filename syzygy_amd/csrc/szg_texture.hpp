@@ -1,8 +1,9 @@
 // szg_texture.hpp — the material sampler of the G-buffer raster pass as device functions, shared by k_raster_tile
 // (kernels_raster.hip), the image passes through szg_image_ops.hpp (decode8: the mip builder, the image copy, the UI layer)
-// and the sampler test kernel (tests/mipsample/mipsample.hip). The rules are those of include/szg/raster.h "textures" (one level) and
-// include/szg/mipmaps.h "SAMPLER" (a registered chain); every translation unit that includes this is built with
-// -ffp-contract=off, so each operation below rounds once.
+// and the sampler test kernels (tests/mipsample/mipsample.hip, tests/anisosample/anisosample.hip). The rules are those of
+// include/szg/raster.h "textures" (one level), include/szg/mipmaps.h "SAMPLER" (a registered chain) and
+// include/szg/anisotropy.h "SAMPLER" (a chain under maxAnisotropy > 1); every translation unit that includes this is built
+// with -ffp-contract=off, so each operation below rounds once.
 #ifndef SZG_TEXTURE_HPP
 #define SZG_TEXTURE_HPP
 
@@ -124,6 +125,80 @@ SZG_DEV V3 sampleTextureMips(const szg_texture& tex, TextureMips mips, V2 st, V2
     V3 const hi = sampleTexture(mipLevel(tex, mips.chain, d + 1), st, unormTable, srgbTable);
     float const g = 1.0f - f;
     return mk3(g * lo.x + f * hi.x, g * lo.y + f * hi.y, g * lo.z + f * hi.z);
+}
+
+// ---- anisotropy.h "SAMPLER" ----
+// The level behind `lv` = level k of `tex` (k >= 0), without walking the chain again.
+SZG_DEV szg_texture mipLevelAfter(const szg_texture& tex, const void* chain, const szg_texture& lv, int k)
+{
+    szg_texture next;
+    next.data = k == 0 ? chain : static_cast<const unsigned char*>(lv.data) + (size_t)lv.width * lv.height * 4u;
+    next.width = max(1u, tex.width >> (k + 1));
+    next.height = max(1u, tex.height >> (k + 1));
+    next.pitch_bytes = next.width * 4u;
+    next.srgb = tex.srgb;
+    return next;
+}
+
+// One trilinear tap between two levels already looked up: f == 0 reads `lo` alone.
+SZG_DEV V3 trilinearTap(const szg_texture& lo, const szg_texture& hi, float f, V2 st, const float* unormTable,
+                        const float* srgbTable)
+{
+    V3 const a = sampleTexture(lo, st, unormTable, srgbTable);
+    if (f == 0.0f)
+    {
+        return a;
+    }
+    V3 const b = sampleTexture(hi, st, unormTable, srgbTable);
+    float const g = 1.0f - f;
+    return mk3(g * a.x + f * b.x, g * a.y + f * b.y, g * a.z + f * b.z);
+}
+
+// maxAnisotropy in [1, 16] (szg_deferred_set_sampler_anisotropy). Lambda, d, f and the two level descriptors are made once
+// per map; the tap loop runs to the largest N of the wave with the other lanes masked off, and a wave whose lanes all have
+// N == 1 branches over it.
+SZG_DEV V3 sampleTextureAniso(const szg_texture& tex, TextureMips mips, float maxAnisotropy, V2 st, V2 dUvDx, V2 dUvDy,
+                              const float* unormTable, const float* srgbTable)
+{
+    if (mips.levels <= 1u || mips.chain == nullptr || tex.data == nullptr || tex.width == 0u || tex.height == 0u)
+    {
+        return sampleTexture(tex, st, unormTable, srgbTable);
+    }
+    float const mux = dUvDx.x * (float)tex.width, mvx = dUvDx.y * (float)tex.height;
+    float const muy = dUvDy.x * (float)tex.width, mvy = dUvDy.y * (float)tex.height;
+    float const px2 = mux * mux + mvx * mvx, py2 = muy * muy + mvy * mvy;
+    float const r2 = fmaxf(px2, py2), s2 = fminf(px2, py2);
+    float eta = 1.0f;
+    if (maxAnisotropy != 1.0f && r2 > 0.0f && r2 != __builtin_inff())
+    {
+        eta = fminf(sqrtf(r2 / s2), maxAnisotropy);
+    }
+    int const N = (int)ceilf(eta);
+    float lam = !(r2 > 0.0f) ? 0.0f : 0.5f * (szg_logf(r2) * 1.44269504f); // mipmaps.h, and all of it when N == 1
+    if (N > 1)
+    {
+        lam = lam - szg_logf(eta) * 1.44269504f;
+    }
+    lam = fminf(fmaxf(lam, 0.0f), fminf(mips.maxLod, (float)(mips.levels - 1u)));
+    int const d = (int)floorf(lam);
+    float const f = lam - (float)d;
+    szg_texture const lo = mipLevel(tex, mips.chain, d);
+    szg_texture const hi = mipLevelAfter(tex, mips.chain, lo, d); // fetched only where f != 0, and then d + 1 < levels
+    if (N == 1)
+    {
+        return trilinearTap(lo, hi, f, st, unormTable, srgbTable);
+    }
+    V2 const major = px2 >= py2 ? dUvDx : dUvDy;
+    float const parts = (float)(N + 1);
+    V3 acc = splat(0.0f);
+    for (int i = 1; i <= N; i++)
+    {
+        float const t = (float)i / parts - 0.5f;
+        V3 const tap = trilinearTap(lo, hi, f, V2{st.x + t * major.x, st.y + t * major.y}, unormTable, srgbTable);
+        acc = i == 1 ? tap : mk3(acc.x + tap.x, acc.y + tap.y, acc.z + tap.z);
+    }
+    float const n = (float)N;
+    return mk3(acc.x / n, acc.y / n, acc.z / n);
 }
 } // namespace szg
 

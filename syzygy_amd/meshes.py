@@ -210,10 +210,13 @@ def mesh_array(meshes, device=None):
     return arr
 
 
-def register_texture_mips(pipeline, meshes, max_lod=abi.SZG_SAMPLER_MAX_LOD_NONE, device="cuda"):
+def register_texture_mips(pipeline, meshes, max_lod=abi.SZG_SAMPLER_MAX_LOD_NONE, device="cuda", max_anisotropy=1.0):
     """Hand the chains of every mesh built with mipmaps=True to `pipeline` (DeferredShadingPipeline.setTextureMips); returns the
-    number of entries. No such mesh clears the table."""
+    number of entries. No such mesh clears the table. `max_anisotropy` above 1.0 also sets the sampler's maxAnisotropy
+    (include/szg/anisotropy.h); at 1.0 the pipeline keeps the value it has."""
     entries = [e for m in meshes for e in m.texture_mips(device)]
+    if max_anisotropy != 1.0:
+        pipeline.setSamplerAnisotropy(max_anisotropy)
     pipeline.setTextureMips(entries, max_lod)
     return len(entries)
 

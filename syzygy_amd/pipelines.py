@@ -205,6 +205,17 @@ def parse_mipmaps_option(text):
     return value
 
 
+def parse_anisotropy_option(text):
+    """The examples' --anisotropy A switch -> the sampler's max_anisotropy (include/szg/anisotropy.h): a number in 1 .. 16."""
+    try:
+        value = float(text)
+    except ValueError:
+        value = 0.0
+    if not abi.SZG_SAMPLER_MAX_ANISOTROPY_REFERENCE <= value <= abi.SZG_SAMPLER_MAX_ANISOTROPY_LIMIT:
+        raise ValueError(f"{text!r}: expected a number from 1 to 16")
+    return value
+
+
 def generate_mipmaps(texture, srgb, cmd=None):
     """szg_record_generate_mipmaps: the packed chain (levels 1.., a uint8 CUDA tensor; empty for a 1x1 image) of an RGBA8 image,
     a uint8 CUDA tensor [h, w, 4] whose rows may be strided (a pitch wider than w * 4)."""
@@ -663,6 +674,11 @@ class DeferredShadingPipeline:
             table[i].level_count = int(levels)
         check(lib().szg_deferred_set_texture_mips(self._h, table if entries else None, len(entries), float(max_lod)))
         self._mip_keep = entries
+
+    def setSamplerAnisotropy(self, max_anisotropy):
+        """szg_deferred_set_sampler_anisotropy (include/szg/anisotropy.h): the sampler's maxAnisotropy, 1.0 (the reference's, and
+        a new pipeline's) to 16.0; it applies to every map with a registered chain of more than one level."""
+        check(lib().szg_deferred_set_sampler_anisotropy(self._h, float(max_anisotropy)))
 
     def gbuffer(self):
         return lib().szg_deferred_gbuffer(self._h).contents

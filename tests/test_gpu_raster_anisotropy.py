@@ -1,0 +1,291 @@
+"""Anisotropic filtering through szg_deferred_record_gbuffer_raster (include/szg/anisotropy.h): on a receding floor (y-major
+footprints) and on a wall seen at a grazing angle (x-major ones) the level of detail the kernel picks is the one float64
+geometry predicts; switched off, without a chain and after every refusal the frame is the one it was; and the C++ mirror
+(include/szg/pipelines.hpp) makes the same frame as the Python one, bit for bit."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from syzygy_amd import abi, lib, meshes
+from tests import mipmap_model as mm
+from tests.native import build as build_native  # the mirror program has its own Makefile, not a target of tests/Makefile
+from tests import raster_scenes as rs
+from tests import util
+from tests.test_gpu_raster_mipmaps import H, PLANES, PROJECTION, TEX, UV_SCALE, W, Z_FAR, Z_NEAR, Raster, _assert_same_frame, _coded_chain
+from tests.test_raster import _planes_equal
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "anisosample")
+A_MAX = 16.0
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
+    from syzygy_amd import pipelines
+
+    class Ctx:
+        pass
+
+    c = Ctx()
+    c.pl, c.torch = pipelines, torch
+    return c
+
+
+# ---------------------------------------------------------------------------
+# the two scenes: a level-coded colour chain (level k uniform with byte 32 k) on a floor and on a wall
+# ---------------------------------------------------------------------------
+def _material():
+    colour = np.zeros((TEX, TEX, 4), np.uint8)
+    return {"color": (colour, False), "normal": (meshes.constant_texture((127, 127, 255, 0), 16), False),
+            "orm": (meshes.constant_texture((255, 60, 0, 0), 8), False)}
+
+
+def _floor():
+    """The plane y = 1 of tests/test_gpu_raster_mipmaps.py: u = 0.375 x, v = 0.375 z."""
+    corners = [(-64.0, 1.0, Z_NEAR), (64.0, 1.0, Z_NEAR), (64.0, 1.0, Z_FAR), (-64.0, 1.0, Z_FAR)]
+    uv = [(UV_SCALE * x, UV_SCALE * z) for x, _, z in corners]
+    material = _material()
+    return rs.mesh_of(corners, [0, 1, 2, 0, 2, 3, 2, 1, 0, 3, 2, 0], material=material, uv=uv, normal=(0.0, -1.0, 0.0)), material
+
+
+def _wall():
+    """The same plane transposed: x = 1, u = 0.375 z, v = 0.375 y, both windings."""
+    corners = [(1.0, -64.0, Z_NEAR), (1.0, 64.0, Z_NEAR), (1.0, 64.0, Z_FAR), (1.0, -64.0, Z_FAR)]
+    uv = [(UV_SCALE * z, UV_SCALE * y) for _, y, z in corners]
+    material = _material()
+    return rs.mesh_of(corners, [0, 1, 2, 0, 2, 3, 2, 1, 0, 3, 2, 0], material=material, uv=uv, normal=(-1.0, 0.0, 0.0)), material
+
+
+def _pixel_rays():
+    px = (np.arange(W) + 0.5)[None, :] * np.ones((H, 1))
+    py = (np.arange(H) + 0.5)[:, None] * np.ones((1, W))
+    return 2.0 * px / W - 1.0, 2.0 * py / H - 1.0
+
+
+def _floor_uv():
+    ndc_x, ndc_y = _pixel_rays()  # the ray (ndc_x, ndc_y, 1) t meets y = 1 at t = z = 1 / ndc_y
+    with np.errstate(divide="ignore"):
+        z = np.where(ndc_y > 0, 1.0 / np.where(ndc_y > 0, ndc_y, 1.0), np.inf)
+    x = ndc_x * z
+    return np.stack([UV_SCALE * x, UV_SCALE * z], axis=-1), (z >= Z_NEAR) & (z <= Z_FAR) & (np.abs(x) <= 64.0)
+
+
+def _wall_uv():
+    ndc_x, ndc_y = _pixel_rays()  # it meets x = 1 at t = z = 1 / ndc_x
+    with np.errstate(divide="ignore"):
+        z = np.where(ndc_x > 0, 1.0 / np.where(ndc_x > 0, ndc_x, 1.0), np.inf)
+    y = ndc_y * z
+    return np.stack([UV_SCALE * z, UV_SCALE * y], axis=-1), (z >= Z_NEAR) & (z <= Z_FAR) & (np.abs(y) <= 64.0)
+
+
+def _expected(uv, on_surface):
+    """float64: the quad differences the kernel takes (right minus left, bottom minus top) of the uv at the pixel centres, the
+    two footprint axes in texels, their ratio, the tap count and the clamped anisotropic lambda."""
+    left, right = uv[:, 0::2], uv[:, 1::2]
+    top, bottom = uv[0::2], uv[1::2]
+    with np.errstate(invalid="ignore", divide="ignore"):  # pixels beside the surface carry inf; they are never compared
+        ddx = np.repeat(right - left, 2, axis=1)
+        ddy = np.repeat(bottom - top, 2, axis=0)
+        px = np.hypot(ddx[..., 0] * TEX, ddx[..., 1] * TEX)
+        py = np.hypot(ddy[..., 0] * TEX, ddy[..., 1] * TEX)
+        longer, shorter = np.maximum(px, py), np.minimum(px, py)
+        ratio = longer / shorter
+        lam_iso = np.log2(longer)
+        want = np.clip(lam_iso - np.log2(np.minimum(ratio, A_MAX)), 0.0, 7.0)
+        taps = np.ceil(np.minimum(ratio, A_MAX))
+    quad = on_surface[0::2, 0::2] & on_surface[0::2, 1::2] & on_surface[1::2, 0::2] & on_surface[1::2, 1::2]
+    whole_quad = np.repeat(np.repeat(quad, 2, axis=0), 2, axis=1)
+    return {"want": want, "lam_iso": lam_iso, "ratio": ratio, "taps": taps, "x_major": px >= py, "compare": on_surface & whole_quad,
+            "step": np.minimum(px, py) / TEX}  # the smaller per-pixel uv step: unclamped, lambda is its logarithm
+
+
+SCENES = {"floor": (_floor, _floor_uv), "wall": (_wall, _wall_uv)}
+
+
+def _entries(gpu, mesh, material):
+    t = gpu.torch
+    entries = [(mesh.device_texture(material["color"][0]), t.from_numpy(_coded_chain()).cuda(), 8)]
+    for key in ("normal", "orm"):  # uniform at every level: their LOD does not show
+        tex = material[key][0]
+        level0 = mesh.device_texture(tex)
+        entries.append((level0, gpu.pl.generate_mipmaps(level0.view(tex.shape[0], tex.shape[1], 4), False), mm.level_count(tex.shape[1], tex.shape[0])))
+    return entries
+
+
+@pytest.fixture(scope="module")
+def frames(gpu):
+    """Both scenes rastered once per configuration, shared by the tests below."""
+    out = {}
+    for name, (make, _) in SCENES.items():
+        mesh, material = make()
+        cam = rs.camera(PROJECTION)
+        r = Raster(gpu, W, H, cam)
+        entries = _entries(gpu, mesh, material)
+        s = {"mesh": [mesh], "material": material, "cam": cam, "entries": entries}
+        s["base"] = r.record([mesh])
+        r.deferred.setSamplerAnisotropy(A_MAX)  # no table yet: nothing to filter
+        s["aniso_without_table"] = r.record([mesh])
+        r.deferred.setSamplerAnisotropy(1.0)
+        r.deferred.setTextureMips(entries, mm.MAX_LOD_NONE)
+        s["mips"] = r.record([mesh])
+        r.deferred.setSamplerAnisotropy(A_MAX)
+        s["aniso"] = r.record([mesh])
+        r.deferred.setSamplerAnisotropy(1.0)
+        s["off_again"] = r.record([mesh])
+        r.close()
+        out[name] = s
+    return out
+
+
+# ---------------------------------------------------------------------------
+# (a), (b): the level of detail
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["floor", "wall"])
+def test_lod_is_the_one_geometry_predicts(frames, name):
+    planes, depth = frames[name]["aniso"]
+    uv, on_surface = SCENES[name][1]()
+    e = _expected(uv, on_surface)
+    assert np.array_equal(depth > 0, on_surface), "coverage differs from the geometry"
+    compare = e["compare"]
+    share = compare.sum() / on_surface.sum()
+    want = e["want"]
+    got = planes["diffuse"][..., 0].astype(np.float64) * 255.0 / 32.0
+    # the tolerance of tests/test_gpu_raster_mipmaps.py, in levels, from this scene's numbers:
+    #   the fp16 store of a value below 1 moves it by at most 2^-12, times 255 / 32
+    store = 2.0**-12 * 255.0 / 32.0
+    #   the fp32 interpolation of uv moves a quad difference by about 2^-23 |uv|max; relative to the smallest per-pixel uv
+    #   step that enters lambda (here the shorter axis: unclamped, lambda is its logarithm) that is the relative error of the
+    #   footprint, and so (up to 1 / ln 2 against the factor 2 below) of lambda
+    interpolation = 2.0**-23 * np.abs(uv[compare]).max() / e["step"][compare].min()
+    assert store < 2.0**-9 and interpolation < 2.0**-9
+    tolerance = 2.0 * (store + interpolation)
+    err = np.abs(got - want)[compare]
+    taps = e["taps"][compare]
+    clamped = (e["ratio"][compare] >= A_MAX).mean()
+    x_major = e["x_major"][compare].mean()
+    print(f"{name}: surface pixels {on_surface.sum()}, compared {compare.sum()} ({share:.3f}); ratio {e['ratio'][compare].min():.2f} .. "
+          f"{e['ratio'][compare].max():.2f}, {np.unique(taps).size} distinct N, clamped at 16: {clamped:.3f}, x-major {x_major:.3f}; "
+          f"|uv|max {np.abs(uv[compare]).max():.3f}, smallest step {e['step'][compare].min():.6f}: store {store:.3e}, "
+          f"interpolation {interpolation:.3e}; lambda spans {want[compare].min():.3f} .. {want[compare].max():.3f} "
+          f"(trilinear {np.clip(e['lam_iso'], 0, 7)[compare].max():.3f}); max |lam_gpu - lam| {err.max():.3e}, tolerance {tolerance:.3e}")
+    assert share >= 0.9
+    assert err.max() <= tolerance
+    assert want[compare].min() <= 0.05 and want[compare].max() >= 4.0  # the expected lambda spans 0 .. 4.5
+    assert np.unique(taps).size >= 10 and clamped > 0
+    assert (x_major < 0.1) if name == "floor" else (x_major > 0.5)
+    # at least one level finer than trilinear on much of the surface, which is what the filter is for: 0.731 of the compared
+    # pixels on the floor, 0.412 on the wall (float64 geometry)
+    finer = (np.clip(e["lam_iso"], 0, 7) - want)[compare] >= 1.0
+    assert finer.mean() >= (0.7 if name == "floor" else 0.4)
+    # green and blue carry the same codes; specular repeats diffuse (offscreen.frag:72-75)
+    assert np.array_equal(planes["diffuse"][..., 1].view(np.uint16), planes["diffuse"][..., 0].view(np.uint16))
+    assert np.array_equal(planes["specular"].view(np.uint16), planes["diffuse"].view(np.uint16))
+
+
+# ---------------------------------------------------------------------------
+# (c), (d), (e): off is off, and only the sampled planes ever change
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["floor", "wall"])
+def test_anisotropy_1_after_16_restores_the_trilinear_frame(frames, name):
+    s = frames[name]
+    _assert_same_frame(s["off_again"], s["mips"])
+    assert not np.array_equal(s["aniso"][0]["diffuse"].view(np.uint16), s["mips"][0]["diffuse"].view(np.uint16))  # and on is on
+
+
+@pytest.mark.parametrize("name", ["floor", "wall"])
+def test_anisotropy_without_a_table_changes_nothing(frames, name):
+    _assert_same_frame(frames[name]["aniso_without_table"], frames[name]["base"])
+
+
+@pytest.mark.parametrize("name", ["floor", "wall"])
+def test_depth_and_world_position_never_change(frames, name):
+    s = frames[name]
+    for other in ("aniso_without_table", "mips", "aniso", "off_again"):
+        assert np.array_equal(s[other][1].view(np.uint32), s["base"][1].view(np.uint32)), other
+        assert np.array_equal(s[other][0]["worldPosition"].view(np.uint32), s["base"][0]["worldPosition"].view(np.uint32)), other
+    # the normal and ORM maps are uniform at every level: a stored code moves by at most one fp16 step, and only where the
+    # value sits on a rounding boundary (tests/test_gpu_raster_mipmaps.py test_only_the_colour_changes_on_the_plane)
+    for plane in ("normal", "occlusionRoughnessMetallic"):
+        a, b = s["base"][0][plane].astype(np.float64), s["aniso"][0][plane].astype(np.float64)
+        assert (np.abs(a - b) <= 2.0**-10 * np.abs(a) + 2.0**-20).all(), plane
+
+
+def test_default_scene_without_chains_or_with_one_level_entries_equals_the_base_frame(gpu):
+    w, h = 97, 61
+    inp = util.Inputs(w, h)
+    ms = meshes.reference_default_scene()
+    r = Raster(gpu, w, h, inp.cam)
+    base = r.record(ms)
+    assert (base[1] > 0).mean() > 0.05
+    r.deferred.setSamplerAnisotropy(A_MAX)
+    _assert_same_frame(r.record(ms), base)  # no table
+    level0 = {id(tex): m.device_texture(tex) for m in ms for _, _, material in m.surfaces for tex, _ in material.values()}
+    r.deferred.setTextureMips([(t, 0, 1) for t in level0.values()], mm.MAX_LOD_NONE)
+    _assert_same_frame(r.record(ms), base)  # a table of one-level entries
+    r.close()
+
+
+# ---------------------------------------------------------------------------
+# (f) row tiles, (g) refusals
+# ---------------------------------------------------------------------------
+def test_row_tiles_equal_the_untiled_frame(gpu, frames):
+    s = frames["floor"]
+    full_planes, full_depth = s["aniso"]
+    for rank in range(3):
+        tile = util.rowtile(H, 8, rank, 3)
+        rows = util.global_rows(H, 8, rank, 3)
+        r = Raster(gpu, W, H, s["cam"], tile=tile)
+        r.deferred.setTextureMips(s["entries"], mm.MAX_LOD_NONE)
+        r.deferred.setSamplerAnisotropy(A_MAX)
+        planes, depth = r.record(s["mesh"])
+        r.close()
+        assert np.array_equal(depth.view(np.uint32), full_depth[rows].view(np.uint32))
+        _planes_equal(planes, {name: full_planes[name][rows] for name in PLANES})
+
+
+def test_every_refusal_leaves_the_next_frame_unchanged(gpu, frames):
+    s = frames["wall"]
+    r = Raster(gpu, W, H, s["cam"])
+    r.deferred.setTextureMips(s["entries"], mm.MAX_LOD_NONE)
+    for accepted, reference in ((A_MAX, "aniso"), (1.0, "mips")):
+        r.deferred.setSamplerAnisotropy(accepted)
+        for value in (float("nan"), 0.0, 0.999, -16.0, 16.5, float("inf")):
+            assert lib().szg_deferred_set_sampler_anisotropy(r.deferred._h, value) == abi.SZG_ERR_INVALID_ARGUMENT
+            assert b"szg_deferred_set_sampler_anisotropy" in lib().szg_last_error()
+        assert lib().szg_deferred_set_sampler_anisotropy(None, 4.0) == abi.SZG_ERR_INVALID_ARGUMENT
+        _assert_same_frame(r.record(s["mesh"]), s[reference])
+    r.close()
+
+
+# ---------------------------------------------------------------------------
+# the C++ mirror
+# ---------------------------------------------------------------------------
+def test_the_cpp_mirror_makes_the_same_frame(gpu, frames, tmp_path):
+    s = frames["floor"]
+    mesh = s["mesh"][0]
+    exe = build_native("raster_anisotropy", directory=HERE, hashed=[os.path.join(HERE, "raster_anisotropy.cpp")])
+    mesh.vertices.tofile(tmp_path / "vertices.bin")
+    mesh.indices.tofile(tmp_path / "indices.bin")
+    mesh._models_np.tofile(tmp_path / "models.bin")
+    mesh._mits_np.tofile(tmp_path / "mits.bin")
+    (tmp_path / "camera.bin").write_bytes(bytes(s["cam"]))
+    for key, (level0, chain, _) in zip(("color", "normal", "orm"), s["entries"]):
+        s["material"][key][0].tofile(tmp_path / f"{key}.bin")
+        assert np.array_equal(level0.cpu().numpy(), s["material"][key][0].reshape(-1))
+        chain.cpu().numpy().tofile(tmp_path / f"{key}_chain.bin")
+    p = subprocess.run([exe, str(tmp_path), str(W), str(H), str(A_MAX)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.strip().splitlines()[-1] == f"OK {W} {H} 16"
+    planes, depth = s["aniso"]
+    assert np.array_equal(np.fromfile(tmp_path / "out_depth.bin", np.uint32).reshape(H, W), depth.view(np.uint32))
+    got = {name: np.fromfile(tmp_path / f"out_{short}.bin", planes[name].dtype).reshape(H, W, 4)
+           for name, short in (("diffuse", "diffuse"), ("specular", "specular"), ("normal", "normal"), ("worldPosition", "worldPosition"),
+                               ("occlusionRoughnessMetallic", "orm"))}
+    _planes_equal(got, planes)
