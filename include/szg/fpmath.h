@@ -50,7 +50,7 @@ SZG_FP_FN float szg_div_moderate(float n, float d)
 #if defined(__HIP_DEVICE_COMPILE__)
     /* y = RN(1 / d) (v_rcp_f32 + one Newton step: exhaustively verified, tools/verify_div.hip), q0 = RN(n y), then ONE
      * correction with the exact residual (Markstein): the correctly rounded quotient for every operand pair of this domain
-     * (the same sequence as szg_device.hpp divR0, whose verification covers it; a +0 numerator gives +0 like `/`). */
+     * (the same sequence as szg_lean.hpp divR0, whose verification covers it; a +0 numerator gives +0 like `/`). */
     float y = __builtin_amdgcn_rcpf(d);
     y = __builtin_fmaf(__builtin_fmaf(-d, y, 1.0f), y, y);
     float const q0 = n * y;

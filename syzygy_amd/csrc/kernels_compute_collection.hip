@@ -15,8 +15,9 @@
 // texel pairs are formed by ADDRESS: pair g covers the 16 aligned bytes counted from the 16-B boundary at or below the
 // image's first texel, so that a full pair is one aligned 16-B store; a pair that straddles the left or right edge of the
 // written set, or a row whose pitch moves it off the 16-B grid, takes one predicated 8-B store per texel.
-#include "szg_device.hpp"
+#include "szg_formats.hpp"
 #include "szg_launch.hpp"
+#include "szg_vec.hpp"
 
 #include "szg/compute_collection.h"
 

@@ -10,9 +10,13 @@
 //                    scene colour (deferred.cpp:715-717)
 //   k_compose      : HBM-bound row scatter after the RCCL gather
 
-#include "szg_device.hpp"
+#include "szg/fpmath.h"
+#include "szg_formats.hpp"
 #include "szg_launch.hpp"
+#include "szg_lean.hpp"
 #include "szg_light_tiles.hpp"
+#include "szg_pbr.hpp"
+#include "szg_vec.hpp"
 
 namespace szg
 {
@@ -332,7 +336,7 @@ __global__ void k_light_prep(const szg_directional_light_packed* __restrict__ di
 // either axis implies that with a 1 % margin, far above any rounding of the exact evaluation, so rejecting there
 // never changes a result — unless the other axis is NaN. cw == 0 (st = inf/NaN) is not rejected.
 
-// Runtime (wave-uniform) selection between the lean exact ops of szg_device.hpp and the generic operators;
+// Runtime (wave-uniform) selection between the lean exact ops of szg_lean.hpp and the generic operators;
 // both give the IEEE correctly rounded result, the lean ones only inside their operand ranges.
 SZG_DEV float divU(bool lean, float a, float b, float y) { return lean ? divR(a, b, y) : a / b; }
 // numerator of a lean division: 0, or not tiny (the residual of the one-correction division underflows below ~2^-100; its
@@ -456,11 +460,11 @@ SZG_DEV V3 lightContribution(const LightRec& L, const Material& m, bool position
     {
         spectral = cs * shadow;
     }
-    // computeLightContribution, lights.comp:93-108 (brdfMix of szg_device.hpp with the half vector shared above)
+    // computeLightContribution, lights.comp:93-108 (brdfMix of szg_pbr.hpp with the half vector shared above)
     float const hinv = OPTIMISTIC ? divN0(1.0f, sqrtP(hd)) : (lean ? divN(1.0f, sqrtN(hd)) : 1.0f / sqrtf(hd));
     V3 const h = hs * hinv;
     // both pow() without their special-case selects when no lane of the wave has a zero / denormal / non-finite base or a
-    // zero exponent (szg_device.hpp powLean: the same values)
+    // zero exponent (szg_lean.hpp powLean: the same values)
     float const baseSpecular = clampf(dotP(h, m.normal), 0.0f, 1.0f);
     float const baseFresnel = 1.0f - clampf(dotP(h, lightDir), 0.0f, 1.0f);
     // (OPTIMISTIC: both bases lie in [0, 1] and must be >= 2^-126 for powLean: tracked like the other lower bounds, x * 2^96
@@ -641,25 +645,6 @@ __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image de
                                                 unsigned cameraIndex, const LightRec* __restrict__ lights, unsigned lightCount,
                                                 const unsigned long long* __restrict__ tileMasks, unsigned tilesX)
 {
-#ifdef SZG_EXP_LDS_LIGHTS
-    // EXPERIMENT (profiles/r03_experiments.md, north_star "LDS-staged light lists"; not built into libszg_hip.so): the light
-    // records copied to LDS once per workgroup and read from there (broadcast ds_read into VGPRs) instead of scalar loads
-    // into SGPRs. Up to 264 lights (37 KiB: the 256 spots + the moon of C5).
-    __shared__ LightRec s_lights[264];
-    {
-        unsigned const n = min(lightCount, 264u) * (unsigned)(sizeof(LightRec) / 4u);
-        const unsigned* src = reinterpret_cast<const unsigned*>(lights);
-        unsigned* dst = reinterpret_cast<unsigned*>(s_lights);
-        for (unsigned k = threadIdx.x; k < n; k += 256u)
-        {
-            dst[k] = src[k];
-        }
-        __syncthreads();
-    }
-#define SZG_LIGHTS_PTR s_lights /* (the experiment is run with <= 264 lights) */
-#else
-#define SZG_LIGHTS_PTR lights
-#endif
     unsigned x, y;
     pixel_of_thread_bottom_up(x, y);
     if (x >= drawW || y >= localRows)
@@ -716,13 +701,13 @@ __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image de
         if (waveAll(tightPixel))
         {
             float track = 0x1p100f;
-            sum = lightLoop<true>(SZG_LIGHTS_PTR, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, track);
+            sum = lightLoop<true>(lights, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, track);
             done = waveAll(track >= 0x1p-30f);
         }
         if (!done)
         {
             float unused = 0.0f;
-            sum = lightLoop<false>(SZG_LIGHTS_PTR, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, unused);
+            sum = lightLoop<false>(lights, lightCount, tileWords, m, positionModerate, viewDirection, waveFinite, pixelModerate, unused);
         }
     }
     row_ptr<uint2>(color, y)[x] = pack_unorm16x4(sum.x, sum.y, sum.z, 1.0f);

@@ -6,8 +6,12 @@
 // Both are pure VALU/transcendental kernels (bytes written: 1 MiB and 32 MiB at
 // the reference sizes); nothing here is HBM-bound. See DESIGN.md.
 
-#include "szg_device.hpp"
+#include "szg/fpmath.h"
+#include "szg_atmosphere.hpp"
 #include "szg_launch.hpp"
+#include "szg_lean.hpp"
+#include "szg_march.hpp"
+#include "szg_vec.hpp"
 
 namespace szg
 {
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256) void k_transmittance(const szg_atmosphere_pack
     float const distance = hit ? t1 : 0.0f;
     float const dt = distance / 500.0f;
     float const ndt = -fabsf(dt);
-    // lean exact ops (szg_device.hpp) when the atmosphere block and this ray are in their domain; the flag is
+    // lean exact ops (szg_lean.hpp) when the atmosphere block and this ray are in their domain; the flag is
     // wave-uniform so that the loop body exists once per wave
     // smallest squared radius along the ray: at the closest approach when the ray points downwards, else at its origin
     float const rmin2 = mu < 0.0f ? radius * radius * (1.0f - mu * mu) : radius * radius;
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256) void k_lut_range(float4* __restrict__ lut, uns
     }
 }
 
-// One lane: the per-frame constants of szg_device.hpp FramePrep.
+// One lane: the per-frame constants of szg_atmosphere.hpp FramePrep.
 __global__ __launch_bounds__(64) void k_frame_prep(const szg_atmosphere_packed* __restrict__ atmospheres, unsigned atmosphereIndex,
                                                    int tW, int tH, FramePrep* __restrict__ out,
                                                    const szg_directional_light_packed* __restrict__ sun)

@@ -15,9 +15,10 @@
 //   k_shadow_tile    the same walk, depth only (front faces culled, GREATER_OR_EQUAL, depth bias)
 
 #include "szg/exact_sign.h"
-#include "szg_device.hpp"
+#include "szg_formats.hpp"
 #include "szg_launch.hpp"
 #include "szg_texture.hpp"
+#include "szg_vec.hpp"
 
 namespace szg
 {

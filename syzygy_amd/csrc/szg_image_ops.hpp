@@ -6,8 +6,11 @@
 #ifndef SZG_IMAGE_OPS_HPP
 #define SZG_IMAGE_OPS_HPP
 
-#include "szg_device.hpp"
+#include "szg/fpmath.h"
+#include "szg_formats.hpp"
+#include "szg_lean.hpp"
 #include "szg_texture.hpp"
+#include "szg_vec.hpp"
 
 namespace szg
 {

@@ -60,7 +60,7 @@ struct TileArgs
 
 // Transmittance LUT block: W*H RGBA32F texels followed by ONE status dword (16 bytes reserved). The dword is 0 when
 // every texel's rgb lies in [2^-50, 2] — the operand domain in which the march may use the lean exact division for
-// transmittance ratios (szg_device.hpp TLut::moderate). launch_transmittance maintains it; launch_lut_range recomputes
+// transmittance ratios (szg_atmosphere.hpp TLut::moderate). launch_transmittance maintains it; launch_lut_range recomputes
 // it for texels written by the caller. Every kernel that takes `tlut` reads the dword behind the texels.
 inline size_t tlut_block_bytes(unsigned W, unsigned H) { return (size_t)W * H * 16u + 16u; }
 hipError_t launch_lut_range(hipStream_t s, float* lut, unsigned W, unsigned H);
@@ -93,7 +93,7 @@ hipError_t launch_slut_status_reduce(hipStream_t s, const unsigned* d_all, unsig
 hipError_t launch_skyview(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const szg_camera_packed* d_cam,
                           unsigned camIndex, const float* tlut, unsigned tW, unsigned tH, float* lut, unsigned W, unsigned H,
                           unsigned rowBegin, unsigned rowEnd, const unsigned* d_dirty, const void* d_prep);
-// Per-frame constants (szg_device.hpp FramePrep): one-lane kernel in front of the sky-view LUT kernel and the composite, which
+// Per-frame constants (szg_atmosphere.hpp FramePrep): one-lane kernel in front of the sky-view LUT kernel and the composite, which
 // read `d_prep` (frame_prep_bytes() bytes of device memory) instead of deriving the same ~300 instructions' worth in every wave.
 size_t frame_prep_bytes();
 // `d_sun` (may be null): the directional light whose shadow map the composite samples; its TO_TEX * projection * view goes into

@@ -7,8 +7,9 @@
 #ifndef SZG_TEXTURE_HPP
 #define SZG_TEXTURE_HPP
 
+#include "szg/fpmath.h"
 #include "szg/raster.h"
-#include "szg_device.hpp"
+#include "szg_vec.hpp"
 
 namespace szg
 {
