@@ -20,6 +20,19 @@
 #include "szg_pbr.hpp"
 #include "szg_vec.hpp"
 
+// Two switches over what phase A and phase C do outside the march (profiles/composite_pixel_path.md measures each alone;
+// results are the same with either off):
+//   SZG_COMPOSITE_FRAME_CONSTANTS  what depends on the camera, the atmosphere and the draw extent alone is read from
+//                                  FramePrep::Camera (k_frame_prep, once per frame) instead of being formed per pixel
+//   SZG_COMPOSITE_LEAN_PIXEL       the per-pixel quotients, square roots and pow() of phases A and C use the lean exact operators
+//                                  of szg_lean.hpp where a wave-uniform gate proves their operand domain
+#ifndef SZG_COMPOSITE_FRAME_CONSTANTS
+#define SZG_COMPOSITE_FRAME_CONSTANTS 1
+#endif
+#ifndef SZG_COMPOSITE_LEAN_PIXEL
+#define SZG_COMPOSITE_LEAN_PIXEL 1
+#endif
+
 namespace szg
 {
 namespace
@@ -64,11 +77,34 @@ SZG_DEV V3 sampleMapDirection(const SkyLut& S, const Atm& a, V3 position, V3 dir
     return bilinear_rgb(S.texels, S.width, S.height, (float)S.width, (float)S.height, u, v);
 }
 
-// sampleSunDisk, camera.comp:123-140
-SZG_DEV V3 sampleSunDisk(const TLut& L, const Atm& a, V3 position, V3 direction)
+// ... for a ray that starts at the camera: the horizon terms and the projected sun direction are FramePrep::Camera's (the same
+// expressions on the camera's position and the atmosphere, formed once per frame)
+SZG_DEV V3 sampleMapDirection(const SkyLut& S, const FramePrep::Camera& c, V3 direction)
+{
+    V3 const normalized = normalize(direction);
+    float const cosViewZenith = normalized.y;
+    float const viewZenith = szg_acosf(normalized.y);
+    float v;
+    if (cosViewZenith > c.cosHorizonZenith)
+    {
+        float const angleFraction = viewZenith / c.horizonZenith;
+        v = (1.0f - sqrtf(1.0f - angleFraction)) * 0.5f;
+    }
+    else
+    {
+        float const angleFraction = (viewZenith - c.horizonZenith) / c.piMinusHorizon;
+        v = sqrtf(angleFraction) * 0.5f + 0.5f;
+    }
+    V2 const projectedView = normalize(V2{direction.x, direction.z});
+    float const u = clampf(dot(c.projectedLight, projectedView), -1.0f, 1.0f) * 0.5f + 0.5f;
+    return bilinear_rgb(S.texels, S.width, S.height, (float)S.width, (float)S.height, u, v);
+}
+
+// sampleSunDisk, camera.comp:123-140; `sunLength` is length(directionToSun) (FramePrep::Camera::sunLength) where the caller has it
+SZG_DEV V3 sampleSunDisk(const TLut& L, const Atm& a, V3 position, V3 direction, float sunLength)
 {
     V3 const directionToSun = -a.incidentDirectionSun;
-    float const cosDirectionSun = dot(direction, directionToSun) / (length(direction) * length(directionToSun));
+    float const cosDirectionSun = dot(direction, directionToSun) / (length(direction) * sunLength);
     float const sinSunRadius = a.sunAngularRadius;
     float const sinDirectionSun = safeSqrt(1.0f - cosDirectionSun * cosDirectionSun);
     if (cosDirectionSun < 0.0f)
@@ -77,6 +113,10 @@ SZG_DEV V3 sampleSunDisk(const TLut& L, const Atm& a, V3 position, V3 direction)
     }
     V3 const transmittanceToSun = sampleT_Ray(L, a, position, direction);
     return transmittanceToSun * (1.0f - smoothstep(0.2f * sinSunRadius, sinSunRadius, sinDirectionSun));
+}
+SZG_DEV V3 sampleSunDisk(const TLut& L, const Atm& a, V3 position, V3 direction)
+{
+    return sampleSunDisk(L, a, position, direction, length(-a.incidentDirectionSun));
 }
 
 // raycastDistanceToGround, camera.comp:175-192
@@ -200,18 +240,39 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     float const sceneDepth = row_ptr<const float>(depth, y)[x];
 
     // camera.comp:320-322
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+    const FramePrep::Camera& fc = prep->camera; // (scalar loads; read in phase A only)
+    V3 const position = fc.position;
+#else
     V3 position = mk3(cam->position[0], cam->position[1], cam->position[2]) / 1000000.0f;
     position.y *= -1.0f;
     position.y += a.planetRadius;
+#endif
 
     // camera.comp:324-328 (no pixel-centre offset: SURVEY Q5; global row)
-    float const clipx = ((float)x / (float)drawW - 0.5f) * 2.0f;
-    float const clipy = ((float)gy / (float)drawH - 0.5f) * 2.0f;
+#if SZG_COMPOSITE_LEAN_PIXEL
+    // x and the row are 0 or an integer in [1, 2^32), the extents integers in [1, 2^32): inside the domain of divR0 whatever
+    // the frame (no gate), and a zero quotient is +0 as IEEE gives it
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+    float const rcpW = fc.rcpDrawW, rcpH = fc.rcpDrawH;
+#else
+    float const rcpW = rcpN((float)drawW), rcpH = rcpN((float)drawH);
+#endif
+    float const screenx = divR0((float)x, (float)drawW, rcpW), screeny = divR0((float)gy, (float)drawH, rcpH);
+#else
+    float const screenx = (float)x / (float)drawW, screeny = (float)gy / (float)drawH;
+#endif
+    float const clipx = (screenx - 0.5f) * 2.0f;
+    float const clipy = (screeny - 0.5f) * 2.0f;
     M4 const inverseProjection = load_m4(cam->inverseProjection);
     M4 const rotation = load_m4(cam->rotation);
     V4 const dvs = mul(inverseProjection, clipx, clipy, 1.0f, 1.0f);
     V4 const rot = mul(rotation, dvs.x, dvs.y, dvs.z, dvs.w);
-    V3 direction = normalize(mk3(rot.x, rot.y, rot.z));
+    // normalize() as v * (1 / sqrt(dot)) with the lean operators when every lane's squared length is a moderate number
+    V3 const unrotated = mk3(rot.x, rot.y, rot.z);
+    float const unrotated2 = dot(unrotated, unrotated);
+    bool const viewLean = SZG_COMPOSITE_LEAN_PIXEL && waveAll(leanLength2(unrotated2));
+    V3 direction = viewLean ? unrotated * divN0(1.0f, sqrtP(unrotated2)) : normalize(unrotated);
     direction.y *= -1.0f;
 
     // ---- phase A ---------------------------------------------------------
@@ -225,7 +286,11 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         V4 const normal = unpack_half4(row_ptr<const uint2>(g.normal, y)[x]);
         V4 const orm = unpack_half4(row_ptr<const uint2>(g.orm, y)[x]);
         float4 const p4 = row_ptr<const float4>(g.position, y)[x];
-        m = convertPBR(V4{p4.x, p4.y, p4.z, p4.w}, normal, diffuse, specular, orm);
+        // (the quotients by max(specular) and by pi and pow(160, .) with the lean operators when no lane of the wave has a black,
+        // non-finite or negative-max specular, a non-finite diffuse, or a roughness of 1 or beyond fp32's moderate range)
+        bool const materialLean = SZG_COMPOSITE_LEAN_PIXEL && waveAll(convertPBRLeanOK(diffuse, specular, orm));
+        m = materialLean ? convertPBR<true>(V4{p4.x, p4.y, p4.z, p4.w}, normal, diffuse, specular, orm)
+                         : convertPBR<false>(V4{p4.x, p4.y, p4.z, p4.w}, normal, diffuse, specular, orm);
         isSky = m.position.y > 0.0f; // underground, +y down (:354)
     }
 
@@ -250,15 +315,26 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         }
         else
         {
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+            base = sampleMapDirection(S, fc, direction) + sampleSunDisk(L, a, position, direction, fc.sunLength) * 1.0f;
+#else
             base = sampleMapDirection(S, a, position, direction) + sampleSunDisk(L, a, position, direction) * 1.0f;
+#endif
         }
     }
     else
     {
         // camera.comp:364
         uint2 const prior = row_ptr<const uint2>(color, y)[x];
+#if SZG_COMPOSITE_LEAN_PIXEL
+        // (numerators 0 or an integer in [1, 65535]: inside the domain of divR0 for every texel, no gate)
+        float const rcp65535 = rcpN(65535.0f);
+        surfaceLuminance = mk3(divR0((float)(prior.x & 0xFFFFu), 65535.0f, rcp65535), divR0((float)(prior.x >> 16), 65535.0f, rcp65535),
+                               divR0((float)(prior.y & 0xFFFFu), 65535.0f, rcp65535));
+#else
         surfaceLuminance = mk3((float)(prior.x & 0xFFFFu) / 65535.0f, (float)(prior.x >> 16) / 65535.0f,
                                (float)(prior.y & 0xFFFFu) / 65535.0f);
+#endif
 
         // camera.comp:366-369: shadow frame from the engine-space position/normal
         float shadowFactor = 1.0f;
@@ -283,6 +359,8 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         // camera.comp:371-374
         m.normal.y *= -1.0f;
         m.position.y *= -1.0f;
+        // (the quotient by 10^6 stays generic: a lean form's gate would have no observable side - a coordinate beyond 2^60 or below
+        // 2^-60 gives the same pixel either way - and a gate no test can see is not kept, profiles/composite_pixel_path.md)
         m.position = m.position / 1000000.0f;
         m.position.y += a.planetRadius;
 
@@ -290,22 +368,39 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         V3 const surfacePosition = m.position;
         // the two transmittance samples of this branch with the lean exact operators when the whole wave allows it
         V3 const toSurface = surfacePosition - position;
-        bool const samplesLean = waveAll(a.lean && leanRadius2(a, dot(position, position)) && leanRadius2(a, dot(surfacePosition, surfacePosition)) &&
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+        float const cameraR2 = fc.r2;
+#else
+        float const cameraR2 = dot(position, position);
+#endif
+        bool const samplesLean = waveAll(a.lean && leanRadius2(a, cameraR2) && leanRadius2(a, dot(surfacePosition, surfacePosition)) &&
                                          leanLength2(dot(toSurface, toSurface)) &&
                                          leanLength2(dot(a.incidentDirectionSun, a.incidentDirectionSun)));
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+        RadiusPart const cameraPart = cameraRadiusPart(fc);
+        V3 const transmittanceToSurface = samplesLean ? sampleT_Segment<true>(L, a, position, cameraPart, fc.lenFrom, surfacePosition)
+                                                      : sampleT_Segment<false>(L, a, position, cameraPart, fc.lenFrom, surfacePosition);
+#else
         V3 const transmittanceToSurface = samplesLean ? sampleT_Segment<true>(L, a, position, surfacePosition)
                                                       : sampleT_Segment<false>(L, a, position, surfacePosition);
+#endif
         // (normalize(), length() and the quotients below likewise: v * (1 / sqrt(dot)) and sqrt(dot) with the lean operators)
-        V3 const minusSun = -a.incidentDirectionSun, minusDirection = -direction;
+        V3 const minusDirection = -direction;
         float const direction2 = dot(minusDirection, minusDirection);
         bool const vectorsLean = samplesLean && waveAll(leanLength2(direction2));
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+        V3 const lightDirection = fc.lightDirection; // normalize(minusSun)
+#else
+        V3 const minusSun = -a.incidentDirectionSun;
         V3 const lightDirection = vectorsLean ? minusSun * divN0(1.0f, sqrtP(dot(minusSun, minusSun))) : normalize(minusSun);
+#endif
         V3 const viewDirection = vectorsLean ? minusDirection * divN0(1.0f, sqrtP(direction2)) : normalize(minusDirection);
         float pt0 = 0.0f, pt1 = 0.0f;
         bool const shadowedByPlanet = raySphere(surfacePosition, lightDirection, a.planetRadius, pt0, pt1) && pt0 > 0.0f;
         V3 const halfSum = lightDirection + viewDirection;
         bool const brdfLean = vectorsLean && waveAll(inRange(dot(halfSum, halfSum), 0x1p-40f, 8.0f));
-        V3 const brdf = brdfLean ? brdfMix<true>(m, lightDirection, viewDirection) : brdfMix<false>(m, lightDirection, viewDirection);
+        V3 const brdf = brdfLean ? brdfMix<true, SZG_COMPOSITE_LEAN_PIXEL != 0>(m, lightDirection, viewDirection)
+                                 : brdfMix<false>(m, lightDirection, viewDirection);
         V3 const transmittanceToSun = samplesLean ? sampleT_Ray<true>(L, a, surfacePosition, lightDirection)
                                                   : sampleT_Ray<false>(L, a, surfacePosition, lightDirection);
         float const fractionOfSunVisible = vectorsLean ? divN0(a.planetRadius, sqrtP(dot(m.position, m.position)))
@@ -317,7 +412,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         if (FAST)
         {
             // APPROXIMATE extension (abi.h): aerial perspective from the froxel LUT instead of the inline march
-            base = base + sampleAerial(aerial, (float)x / (float)drawW, (float)gy / (float)drawH, l0);
+            base = base + sampleAerial(aerial, screenx, screeny, l0);
         }
         else
         {
@@ -332,12 +427,16 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         // (it is built from the G-buffer normal; found by tests/sweeps/random_sweep_mesh_frames.py: a NaN normal from a degenerate
         // triangle leaves the sun term at 0 through the clamps but makes the environment sample NaN); otherwise the term
         // is evaluated.
-        float const cameraR2 = dot(position, position), surfaceR2 = dot(surfacePosition, surfacePosition);
+        float const surfaceR2 = dot(surfacePosition, surfacePosition);
         float const nBig = 0x1p60f;
         bool const normalFinite = fabsf(m.normal.x) <= nBig && fabsf(m.normal.y) <= nBig && fabsf(m.normal.z) <= nBig;
         // Both horizon angles asin(Rp / r) must exist: the camera's (every texel of the sky-view LUT depends on it) and the
         // surface's (where the LUT is sampled from); same expressions as skyview_LUT.comp:106-112 and camera.comp:75-77.
+#if SZG_COMPOSITE_FRAME_CONSTANTS
+        float const cameraSinHorizon = fc.sinHorizon; // a.planetRadius / length(position)
+#else
         float const cameraSinHorizon = vectorsLean ? divN0(a.planetRadius, sqrtP(cameraR2)) : a.planetRadius / length(position);
+#endif
         bool const aboveGround = cameraSinHorizon <= 1.0f && fractionOfSunVisible <= 1.0f;
         bool const environmentFinite = a.extModerate && a.sunSane && L.moderate && S.finite && normalFinite && aboveGround &&
                                        inRange(cameraR2, a.extFloor2, a.extCeil2) && inRange(surfaceR2, a.extFloor2, a.extCeil2);
@@ -447,7 +546,12 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     // (read again from the frame block, scalar loads, instead of holding three registers across the march)
     V3 const luminance = transfer * mk3(prep->a.sunIntensitySpectrum.x, prep->a.sunIntensitySpectrum.y, prep->a.sunIntensitySpectrum.z);
     V3 const pre = luminance * 10.0f + surfaceLuminance;
-    V3 const out = mk3(szg_powf(pre.x, 1.2f), szg_powf(pre.y, 1.2f), szg_powf(pre.z, 1.2f));
+    // (pow() without its special cases when every lane's three values are positive normal numbers: a black, denormal, negative or
+    // NaN component sends its wave down the generic form)
+    bool const tonemapLean = SZG_COMPOSITE_LEAN_PIXEL &&
+                             waveAll(powLeanOK(pre.x, 1.2f) && powLeanOK(pre.y, 1.2f) && powLeanOK(pre.z, 1.2f));
+    V3 const out = tonemapLean ? mk3(powLean(pre.x, 1.2f), powLean(pre.y, 1.2f), powLean(pre.z, 1.2f))
+                               : mk3(szg_powf(pre.x, 1.2f), szg_powf(pre.y, 1.2f), szg_powf(pre.z, 1.2f));
     row_ptr<uint2>(color, yC)[xC] = pack_unorm16x4(out.x, out.y, out.z, 1.0f);
     if (debug.data != nullptr)
     {

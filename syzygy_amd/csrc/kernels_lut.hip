@@ -147,13 +147,15 @@ __global__ __launch_bounds__(256) void k_lut_range(float4* __restrict__ lut, uns
 // One lane: the per-frame constants of szg_atmosphere.hpp FramePrep.
 __global__ __launch_bounds__(64) void k_frame_prep(const szg_atmosphere_packed* __restrict__ atmospheres, unsigned atmosphereIndex,
                                                    int tW, int tH, FramePrep* __restrict__ out,
-                                                   const szg_directional_light_packed* __restrict__ sun)
+                                                   const szg_directional_light_packed* __restrict__ sun,
+                                                   const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex, unsigned drawW,
+                                                   unsigned drawH)
 {
     if (threadIdx.x != 0u)
     {
         return;
     }
-    FramePrep f;
+    FramePrep f{};
     f.a = load_atm(atmospheres + atmosphereIndex);
     f.fwidth = (float)tW;
     f.fheight = (float)tH;
@@ -197,6 +199,48 @@ __global__ __launch_bounds__(64) void k_frame_prep(const szg_atmosphere_packed* 
         {
             f.sunShadow[k] = sm.m[k];
         }
+    }
+    if (cameras != nullptr)
+    {
+        // FramePrep::Camera: the expressions of k_composite's phase A, sampleMapDirection, sampleSunDisk and sampleT_Segment that
+        // read nothing of the pixel, with the generic operators
+        float const PI = 3.141592653589793f;
+        const szg_camera_packed* cam = cameras + cameraIndex;
+        FramePrep::Camera& c = f.camera;
+        V3 position = mk3(cam->position[0], cam->position[1], cam->position[2]) / 1000000.0f; // camera.comp:320-322
+        position.y *= -1.0f;
+        position.y += f.a.planetRadius;
+        c.position = position;
+        c.r2 = dot(position, position);
+        c.sinHorizon = f.a.planetRadius / length(position); // camera.comp:75, :144-147
+        c.horizonZenith = PI - szg_asinf(c.sinHorizon);
+        c.cosHorizonZenith = -safeSqrt(1.0f - c.sinHorizon * c.sinHorizon);
+        c.piMinusHorizon = PI - c.horizonZenith;
+        V3 const directionToSun = -f.a.incidentDirectionSun;
+        c.projectedLight = normalize(V2{-f.a.incidentDirectionSun.x, -f.a.incidentDirectionSun.z});
+        c.sunLength = length(directionToSun);
+        c.lightDirection = normalize(directionToSun);
+        TLut L{};
+        L.width = tW;
+        L.height = tH;
+        L.fwidth = f.fwidth;
+        L.fheight = f.fheight;
+        L.u_bias = f.u_bias;
+        L.u_scale = f.u_scale;
+        L.v_bias = f.v_bias;
+        L.v_scale = f.v_scale;
+        c.lenFrom = lengthA(position);
+        RadiusPart const p = radiusPart<false>(L, f.a, c.lenFrom);
+        c.from_r2 = p.r2;
+        c.from_d_min = p.d_min;
+        c.from_denom = p.denom;
+        c.from_rcpDenom = rcpN(p.denom);
+        c.from_b = p.b;
+        c.from_omb = p.omb;
+        c.from_row0 = p.row0;
+        c.from_row1 = p.row1;
+        c.rcpDrawW = rcpN((float)drawW);
+        c.rcpDrawH = rcpN((float)drawH);
     }
     *out = f;
 }
@@ -539,9 +583,11 @@ hipError_t launch_lut_key(hipStream_t s, const szg_atmosphere_packed* d_atm, uns
 
 size_t frame_prep_bytes() { return sizeof(FramePrep); }
 hipError_t launch_frame_prep(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, unsigned tW, unsigned tH, void* d_prep,
-                             const szg_directional_light_packed* d_sun)
+                             const szg_directional_light_packed* d_sun, const szg_camera_packed* d_cam, unsigned camIndex, unsigned drawW,
+                             unsigned drawH)
 {
-    hipLaunchKernelGGL(k_frame_prep, dim3(1), dim3(64), 0, s, d_atm, atmIndex, (int)tW, (int)tH, static_cast<FramePrep*>(d_prep), d_sun);
+    hipLaunchKernelGGL(k_frame_prep, dim3(1), dim3(64), 0, s, d_atm, atmIndex, (int)tW, (int)tH, static_cast<FramePrep*>(d_prep), d_sun,
+                       d_cam, camIndex, drawW, drawH);
     return hipGetLastError();
 }
 

@@ -317,6 +317,25 @@ struct FramePrep
     // TLut::rowsInterior (k_frame_prep evaluates the LUT's v coordinate at both ends of the INNER radius range: the map is
     // monotone, every operation in it being correctly rounded)
     unsigned rowsInterior;
+    // What phase A of the composite derives from the camera block, the atmosphere block and the draw extent alone
+    // (camera.comp:320-322, :75-77, :113, :125-126, :144-147, common.glinl:114-136), formed by k_frame_prep with the generic
+    // operators - which are right in every operand domain, and what the lean ones return inside theirs - through the same
+    // functions on the same inputs. Valid in the block of a record call that hands k_frame_prep a camera (the composite's).
+    // Read in phase A only: nothing of it is live across the march.
+    struct Camera
+    {
+        V3 position;                 // camera position / 1e6, y flipped, + planetRadius
+        float r2, sinHorizon;        // dot(position, position); planetRadius / length(position)
+        float horizonZenith, cosHorizonZenith, piMinusHorizon; // sampleMap_Direction's horizon terms for a ray from the camera
+        V2 projectedLight;           // normalize(vec2(-sun.x, -sun.z))
+        float sunLength;             // length(-sun) (SZG_C_DOT; Atm::sunLength is the SZG_C_ATMODOT one)
+        V3 lightDirection;           // normalize(-sun)
+        // radiusPart(lengthA(position)) of sampleT_Segment's `from` side, field by field, and rcpN of its denominator for the
+        // lean form (meaningful where the lean gate of the call holds, which is the only case it is read in)
+        float lenFrom, from_r2, from_d_min, from_denom, from_rcpDenom, from_b, from_omb;
+        unsigned from_row0, from_row1;
+        float rcpDrawW, rcpDrawH;    // rcpN((float)drawW), rcpN((float)drawH): the clip coordinates' shared reciprocals
+    } camera;
 };
 // The block arrives through scalar loads; its floats then move to vector registers, where the per-wave derivation used to
 // leave them: a VALU instruction of gfx950 reads at most one scalar operand, and ~70 constants held in scalar registers
@@ -419,6 +438,20 @@ struct RadiusPart
     unsigned row1;      // SGPR-base + VGPR-offset addressing instead of 64-bit VALU address arithmetic
     float b, omb;       // v weight and 1 - b
 };
+SZG_DEV RadiusPart cameraRadiusPart(const FramePrep::Camera& c)
+{
+    RadiusPart p;
+    p.r = c.lenFrom;
+    p.r2 = c.from_r2;
+    p.d_min = c.from_d_min;
+    p.denom = c.from_denom;
+    p.rcpDenom = c.from_rcpDenom;
+    p.row0 = c.from_row0;
+    p.row1 = c.from_row1;
+    p.b = c.from_b;
+    p.omb = c.from_omb;
+    return p;
+}
 template <bool LEAN = false, bool INNER = false> SZG_DEV RadiusPart radiusPart(const TLut& L, const Atm& a, float radius)
 {
     RadiusPart p;
@@ -569,6 +602,23 @@ SZG_DEV V3 segmentRatio(const TLut& L, const Atm& a, const RadiusPart& pFrom, fl
     }
     V3 const q = flip ? (Tt / Tf) : (Tf / Tt);
     return clamp01(q);
+}
+// sampleT_Segment with the radius part and the length of the `from` side handed in (FramePrep::Camera: the camera's, once per
+// frame): radiusPart<LEAN>(L, a, lenFrom) and lenFrom = |from| as the form below derives them
+template <bool LEAN = false> SZG_DEV V3 sampleT_Segment(const TLut& L, const Atm& a, V3 from, const RadiusPart& pf, float lenFrom, V3 to)
+{
+    if (LEAN)
+    {
+        V3 const segment = to - from;
+        V3 const direction = segment * divN0(1.0f, sqrtP(dotA(segment, segment))); // normalizeA()
+        float const lenTo = sqrtP(dotA(to, to));
+        RadiusPart const pt = radiusPart<true>(L, a, lenTo);
+        return segmentRatio<true>(L, a, pf, dotA(from, direction), lenFrom, pt, dotA(to, direction), lenTo, sqrtP(dotA(direction, direction)));
+    }
+    V3 const direction = normalizeA(to - from);
+    float const lenTo = lengthA(to);
+    RadiusPart const pt = radiusPart<false>(L, a, lenTo);
+    return segmentRatio<false>(L, a, pf, dotA(from, direction), lenFrom, pt, dotA(to, direction), lenTo, lengthA(direction));
 }
 template <bool LEAN = false> SZG_DEV V3 sampleT_Segment(const TLut& L, const Atm& a, V3 from, V3 to)
 {

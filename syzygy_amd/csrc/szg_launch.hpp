@@ -97,9 +97,11 @@ hipError_t launch_skyview(hipStream_t s, const szg_atmosphere_packed* d_atm, uns
 // read `d_prep` (frame_prep_bytes() bytes of device memory) instead of deriving the same ~300 instructions' worth in every wave.
 size_t frame_prep_bytes();
 // `d_sun` (may be null): the directional light whose shadow map the composite samples; its TO_TEX * projection * view goes into
-// the block (FramePrep::sunShadow).
+// the block (FramePrep::sunShadow). `d_cam` (may be null), `camIndex`, `drawW`, `drawH`: the composite's camera and draw extent;
+// what phase A derives from them and the atmosphere alone goes into the block (FramePrep::Camera).
 hipError_t launch_frame_prep(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, unsigned tW, unsigned tH, void* d_prep,
-                             const szg_directional_light_packed* d_sun = nullptr);
+                             const szg_directional_light_packed* d_sun = nullptr, const szg_camera_packed* d_cam = nullptr,
+                             unsigned camIndex = 0u, unsigned drawW = 0u, unsigned drawH = 0u);
 hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount, unsigned dirSkip,
                              const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_slots,
                              unsigned slotCount, LightRec* d_out);

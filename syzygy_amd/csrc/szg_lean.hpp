@@ -111,6 +111,8 @@ SZG_DEV float xorSign(float x, unsigned signMask)
 }
 SZG_DEV bool inRange(float x, float lo, float hi) { return x >= lo && x <= hi; } // false for NaN
 SZG_DEV float divN0(float a, float b) { return divR0(a, b, rcpN(b)); }
+// a numerator divR / divR0 accept: +-0, or a magnitude in [2^-60, 2^60] (false for NaN)
+SZG_DEV bool leanQuotientOperand(float a) { return a == 0.0f || inRange(fabsf(a), 0x1p-60f, 0x1p60f); }
 // true when `c` holds on every active lane: one compare into a lane mask and one scalar test (HIP's __all() builds two
 // ballots from an int predicate, ~15 instructions per use). Lanes switched off by divergence - a call under a divergent `if`,
 // lanes that have left the kernel - do not take part: the ballot has 0 for them, so their values can neither open nor close a

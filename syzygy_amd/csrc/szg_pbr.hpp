@@ -25,36 +25,59 @@ struct Material
     float normalization;
 };
 
-// pbrFunctions.glinl:3-20
-SZG_DEV Material convertPBR(V4 position, V4 normal, V4 diffuse, V4 specular, V4 orm)
+// Per-pixel precondition of convertPBR<true> (the caller asks it of every lane of the wave): the largest specular component,
+// the denominator of the three reflectance quotients, a positive moderate number - a black specular makes it 0 - and their
+// numerators, like the three of subscattering / pi, zeros or moderate numbers; pow(160, 1 - roughness) inside powLean's
+// domain - a roughness of 1 makes the exponent 0.
+SZG_DEV bool convertPBRLeanOK(V4 diffuse, V4 specular, V4 orm)
+{
+    float const mx = fmaxf(fmaxf(specular.x, specular.y), specular.z);
+    return inRange(mx, 0x1p-60f, 0x1p60f) && leanQuotientOperand(0.5f * specular.x) && leanQuotientOperand(0.5f * specular.y) &&
+           leanQuotientOperand(0.5f * specular.z) && leanQuotientOperand(diffuse.x) && leanQuotientOperand(diffuse.y) && leanQuotientOperand(diffuse.z) &&
+           powLeanOK(160.0f, 1.0f - orm.y);
+}
+// pbrFunctions.glinl:3-20. LEAN (convertPBRLeanOK on every lane): the quotients with one shared reciprocal per denominator and
+// the sign IEEE gives a zero quotient, pow() without its special cases - the same values.
+template <bool LEAN = false> SZG_DEV Material convertPBR(V4 position, V4 normal, V4 diffuse, V4 specular, V4 orm)
 {
     Material m;
     V3 const spec = mk3(specular.x, specular.y, specular.z);
     float const mx = fmaxf(fmaxf(spec.x, spec.y), spec.z);
-    V3 const metallicReflectance = (splat(0.5f) * spec) / mx;
+    V3 const halfSpec = splat(0.5f) * spec;
+    float const rcpMx = LEAN ? rcpN(mx) : 0.0f;
+    V3 const metallicReflectance = LEAN ? mk3(divR(halfSpec.x, mx, rcpMx), divR(halfSpec.y, mx, rcpMx), divR(halfSpec.z, mx, rcpMx))
+                                        : halfSpec / mx;
     m.position = mk3(position.x, position.y, position.z);
     m.normal = mk3(normal.x, normal.y, normal.z);
     m.subscattering = mk3(diffuse.x, diffuse.y, diffuse.z);
     m.metallic = orm.z;
     m.reflectance = mix(splat(0.04f), metallicReflectance, splat(m.metallic));
     m.occlusion = orm.x;
-    m.specularPower = szg_powf(160.0f, 1.0f - orm.y);
-    m.diffuse = m.subscattering / 3.14159265359f;
+    m.specularPower = LEAN ? powLean(160.0f, 1.0f - orm.y) : szg_powf(160.0f, 1.0f - orm.y);
+    float const pi = 3.14159265359f;
+    float const rcpPi = LEAN ? rcpN(pi) : 0.0f;
+    m.diffuse = LEAN ? mk3(divR(m.subscattering.x, pi, rcpPi), divR(m.subscattering.y, pi, rcpPi), divR(m.subscattering.z, pi, rcpPi))
+                     : m.subscattering / pi;
     m.normalization = (m.specularPower + 2.0f) / 8.0f;
     return m;
 }
 
 // computeLightContribution's BRDF part (lights.comp:93-108 / camera.comp:258-271):
 // mix(diffuseBRDF, specularBRDF, fresnel) for outgoing light/view directions. LEAN: the caller has checked
-// that |lightDir + viewDir|^2 >= 2^-40 (normalisation with the lean exact ops).
-template <bool LEAN = false> SZG_DEV V3 brdfMix(const Material& m, V3 lightDir, V3 viewDir)
+// that |lightDir + viewDir|^2 >= 2^-40 (normalisation with the lean exact ops). POWS: both pow() without their special-case
+// selects when no lane of the wave has a zero / denormal base or an exponent outside powLean's domain (as lightContribution
+// of the lights pass does).
+template <bool LEAN = false, bool POWS = false> SZG_DEV V3 brdfMix(const Material& m, V3 lightDir, V3 viewDir)
 {
     V3 const hs = lightDir + viewDir;
     float const hd = dotP(hs, hs);
     V3 const h = hs * divX<LEAN>(1.0f, sqrtX<LEAN>(hd));
-    float const microfacet = szg_powf(clampf(dotP(h, m.normal), 0.0f, 1.0f), m.specularPower);
+    float const baseSpecular = clampf(dotP(h, m.normal), 0.0f, 1.0f);
+    float const baseFresnel = 1.0f - clampf(dotP(h, lightDir), 0.0f, 1.0f);
+    bool const powsLean = POWS && waveAll(powLeanOK(baseSpecular, m.specularPower) && powLeanOK(baseFresnel, 5.0f));
+    float const microfacet = powsLean ? powLean(baseSpecular, m.specularPower) : szg_powf(baseSpecular, m.specularPower);
     V3 const specular = splat(m.normalization * microfacet);
-    float const p = szg_powf(1.0f - clampf(dotP(h, lightDir), 0.0f, 1.0f), 5.0f);
+    float const p = powsLean ? powLean(baseFresnel, 5.0f) : szg_powf(baseFresnel, 5.0f);
     V3 const fresnel = m.reflectance + (splat(1.0f) - m.reflectance) * p;
     return mix(m.diffuse, specular, fresnel);
 }
