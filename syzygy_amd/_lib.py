@@ -18,8 +18,9 @@ class SzgError(RuntimeError):
 
 
 def library_path():
-    # SZG_HIP_LIBRARY: tests/test_gpu_spirv_pin.py and tests/test_gpu_contraction_whole_images.py point child processes at
-    # csrc/libszg_hip_literal.so (the same kernels with the contraction rule switched off); nothing else sets it
+    # SZG_HIP_LIBRARY: tests/test_gpu_spirv_pin.py, tests/test_gpu_contraction_whole_images.py and tests/test_gpu_literal_gates.py
+    # point child processes at csrc/libszg_hip_literal.so (the same kernels with the contraction rule switched off); nothing
+    # else sets it
     return os.environ.get("SZG_HIP_LIBRARY") or os.path.join(_HERE, "csrc", "libszg_hip.so")
 
 

@@ -19,6 +19,7 @@ import numpy as np
 
 from syzygy_amd import abi
 from tests import composite_gate_cases as cg
+from tests import literal_pair as lp
 
 f32 = np.float32
 TLUT_EXTENT, SLUT_EXTENT = (64, 16), (128, 64)
@@ -294,6 +295,7 @@ def describe(frame, y, x, got, want):
 def assert_same(frame, debug, color, want_debug, want_color, what):
     """Bit for bit with no value excluded: the fp32 debug image (NaN for NaN) and the UNORM16 colour."""
     assert debug.shape == want_debug.shape and color.shape == want_color.shape
+    lp.compared(want_debug.size + want_color.size)
     same = (debug.view(np.uint32) == want_debug.view(np.uint32)) | (np.isnan(debug) & np.isnan(want_debug))
     bad = np.argwhere(~same.all(axis=-1))
     if len(bad):

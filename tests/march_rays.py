@@ -508,7 +508,8 @@ class Variant:
 
     def __init__(self, name, atm, extent=BASE_EXTENT, poke=None, rows_interior=None, **flags):
         self.name, self.atm, self.extent, self.poke = name, atm, extent, poke
-        # TLut::rowsInterior behind k_frame_prep, where a test relies on its value: read from the device, written down here
+        # TLut::rowsInterior behind k_frame_prep, where a test relies on its value: read from the device, written down here.
+        # A dict where the two builds differ: {"product": ..., "literal": ...} (tests/literal_pair.py)
         self.rows_interior = rows_interior
         self.flags = dict(lean=1, signClearCoefficients=1, zeroAbsorptionRayleigh=1, zeroScatteringOzone=1, extModerate=1, moderate=1)
         self.flags.update(flags)
@@ -537,7 +538,7 @@ def _edited(**fields):
 
 
 VARIANT_NAMES = ("earth", "rayleigh-absorption", "ozone-scattering", "negative-coefficient", "thin-density-scale", "lut-texel-2^-60",
-                 "lut-256x64", "lut-33x7", "lut-33x25", "sun-70", "sun-5", "sun--3")
+                 "lut-256x64", "lut-33x7", "lut-33x25", "lut-33x41", "sun-70", "sun-5", "sun--3")
 
 
 def variants():
@@ -555,8 +556,13 @@ def variants():
         Variant("lut-256x64", e, extent=(256, 64), rows_interior=1),
         Variant("lut-33x7", e, extent=(33, 7), rows_interior=1),
         # (256, 64) and (33, 7) read the same rowsInterior, set; with 25 rows the v coordinate of the lowest radius,
-        # fma(fl(0.5 / 25), 25, -0.5), comes out below 0 and k_frame_prep leaves the flag clear
-        Variant("lut-33x25", e, extent=(33, 25), rows_interior=0),
+        # fma(fl(0.5 / 25), 25, -0.5), comes out below 0 and k_frame_prep leaves the flag clear. That is the product: the
+        # coordinate is a contraction site (SZG_C_TEXCOORD). The literal build rounds twice, fl(fl(0.5 / 25) * 25) - 0.5 = 0
+        # exactly, in k_frame_prep and in radiusPart alike, and sets the flag: row 0 is interior there
+        Variant("lut-33x25", e, extent=(33, 25), rows_interior={"product": 0, "literal": 1}),
+        # with 41 rows fl(0.5 / 41) * 41 lies so far below 0.5 that it rounds to the float below 0.5: the coordinate is -2^-25
+        # with two roundings and about -1.9e-8 with one, and the flag is clear in both builds
+        Variant("lut-33x41", e, extent=(33, 41), rows_interior=0),
         Variant("sun-70", earth(70.0)),
         Variant("sun-5", earth(5.0)),
         Variant("sun--3", earth(-3.0)),

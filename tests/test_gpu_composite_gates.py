@@ -19,6 +19,7 @@ import pytest
 
 from syzygy_amd import abi
 from tests import composite_gate_cases as cg
+from tests import literal_pair as lp
 from tests import padded_images as pi
 
 pytestmark = pytest.mark.gpu
@@ -65,6 +66,7 @@ def describe_mismatch(group, y, x, got, want):
 
 def assert_same_image(group, debug, color, want_debug, want_color, what):
     assert debug.shape == want_debug.shape and color.shape == want_color.shape
+    lp.compared(want_debug.size + want_color.size)
     same = (debug.view(np.uint32) == want_debug.view(np.uint32)) | (np.isnan(debug) & np.isnan(want_debug))
     bad = np.argwhere(~same.all(axis=-1))
     if len(bad):

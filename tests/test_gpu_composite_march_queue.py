@@ -5,6 +5,7 @@ for bit against the oracle: the debug image (with its NaN pattern) and the UNORM
 import numpy as np
 import pytest
 
+from tests import literal_pair as lp
 from tests import util
 from tests.test_gpu_parity import gpu, run_composite_case  # noqa: F401  (gpu is a fixture)
 
@@ -15,7 +16,8 @@ SMALL_LUTS = ((256, 64), (128, 64))
 
 def assert_bit_identical(got, got_q, frame, what):
     want = frame.debug
-    assert got.shape == want.shape, what
+    assert got.shape == want.shape and got_q.shape == frame.color.shape, what
+    lp.compared(want.size + frame.color.size)
     assert (np.isnan(got) == np.isnan(want)).all(), f"{what}: NaN pattern differs"
     ok = ~np.isnan(want)
     differing = int((got.view(np.uint32)[ok] != want.view(np.uint32)[ok]).sum())

@@ -14,6 +14,7 @@ import pytest
 
 from syzygy_amd import abi
 from tests import lights_gate_cases as lg
+from tests import literal_pair as lp
 from tests import padded_images as pi
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,7 @@ def describe_mismatch(group, L, y, x, got, want):
 def assert_same_image(group, L, debug, color, what):
     want_debug, want_color = lg.oracle_frame(group, L)
     assert debug.shape == want_debug.shape and color.shape == want_color.shape
+    lp.compared(want_debug.size + want_color.size)
     same = (debug.view(np.uint32) == want_debug.view(np.uint32)) | (np.isnan(debug) & np.isnan(want_debug))
     bad = np.argwhere(~same.all(axis=-1))
     if len(bad):

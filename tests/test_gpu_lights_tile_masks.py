@@ -10,6 +10,7 @@ import pytest
 
 from syzygy_amd import abi, scene
 from tests import light_tile_model as lt
+from tests import literal_pair as lp
 from tests import padded_images as pi
 from tests import stream_order as so
 from tests import util
@@ -122,6 +123,8 @@ def run(gpu, W, H, spots, n_spots, n_dirs=2, skip=1, edit=None, tile=None, padde
             target.color.assert_outside_untouched((W, rows), "colour")
         else:
             debug, color = target.debug.cpu().numpy(), target.color_numpy()
+        assert debug.shape == frame.debug.shape and color.shape == frame.color.shape
+        lp.compared(frame.debug.size + frame.color.size)
         bad = np.argwhere(~same_bits(debug, frame.debug).all(axis=-1))
         assert len(bad) == 0, f"{len(bad)} texels of the debug image differ from the oracle; first (y, x) = {bad[0]}: " \
                               f"{debug[tuple(bad[0])]} against {frame.debug[tuple(bad[0])]}"

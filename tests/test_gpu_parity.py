@@ -31,6 +31,15 @@ def gpu():
     return c
 
 
+def assert_same_bits(got, want, what):
+    """Every float bit-identical to the oracle's, NaN for NaN: what the README claims of every pass."""
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape, what
+    bad = np.argwhere(~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))))
+    assert len(bad) == 0, f"{what}: {len(bad)} of {want.size} values differ in their bits from the oracle; first at {tuple(bad[0])}: " \
+                          f"{got[tuple(bad[0])]!r} against {want[tuple(bad[0])]!r}"
+
+
 def staged(gpu, inp):
     pl, abi = gpu.pl, gpu.abi
     cameras = pl.TStagedBuffer(abi.CameraPacked, 1)
@@ -60,6 +69,7 @@ def test_transmittance_lut_matches_oracle(gpu, extent):
     worst = assert_close(got, want, atol=1e-12, what=f"transmittance {extent}")
     exact = float((got == want).mean())
     print(f"transmittance {extent}: worst/tol {worst:.3f}, bit-identical fraction {exact:.3f}")
+    assert_same_bits(got, want, f"transmittance {extent}")
     sky.destroy()
 
 
@@ -80,6 +90,7 @@ def test_skyview_lut_matches_oracle(gpu, elevation):
     worst = assert_close(got[..., :3], want[..., :3], atol=1e-9, what=f"skyview elev {elevation}")
     assert (got[..., 3] == 1.0).all()
     print(f"skyview elev {elevation}: worst/tol {worst:.3f}")
+    assert_same_bits(got, want, f"skyview elev {elevation}")
     sky.destroy()
 
 
@@ -841,6 +852,8 @@ def test_aerial_lut_matches_oracle(gpu, elevation, max_distance):
     assert_close(got_tr, want_tr, atol=1e-12, what="aerial transmittance")
     exact = float((got_lum.view(np.uint32) == want_lum.view(np.uint32)).mean())
     print(f"aerial LUT elev {elevation}: bit-identical fraction {exact:.4f}")
+    assert_same_bits(got_lum, want_lum, "aerial luminance")
+    assert_same_bits(got_tr, want_tr, "aerial transmittance")
     vol = got_lum.reshape(32, 32, 32, 4)
     if np.isfinite(vol).all():  # (froxel rays longer than the distance to the ground are NaN in the reference math too)
         assert (vol[1:, :, :, :3].sum((1, 2, 3)) >= vol[:-1, :, :, :3].sum((1, 2, 3))).all()  # in-scatter grows with depth
@@ -962,6 +975,7 @@ def test_multiscatter_lut_matches_its_oracle(gpu):
     assert got.shape == (32, 32, 4)
     assert_close(got, want, atol=1e-12, what="multi-scattering LUT")
     print(f"multi-scatter LUT: bit-identical fraction {float((got.view(np.uint32) == want.view(np.uint32)).mean()):.4f}")
+    assert_same_bits(got, want, "multi-scattering LUT")
     sky.destroy()
 
 
