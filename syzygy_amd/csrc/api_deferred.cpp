@@ -309,9 +309,8 @@ int szg_deferred_record_lights(szg_deferred_t* p, void* stream, szg_rect draw_re
     {
         SZG_HIP(szg::launch_light_tiles(s, draw_rect.width, draw_rect.height, t, p->gbuffer, p->d_lightRecs, lightCount,
                                         p->d_lightTileMasks));
-        unsigned const rows = t.nranks <= 1u ? draw_rect.height : t.local_rows;
         p->lightTilesX = (draw_rect.width + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM;
-        p->lightTilesY = (rows + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM;
+        p->lightTilesY = (t.local_rows + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM;
         p->lightTileBatches = (lightCount + LIGHT_TILE_BATCH - 1u) / LIGHT_TILE_BATCH;
     }
     SZG_HIP(szg::launch_lights(s, *scene_texture, draw_rect.width, draw_rect.height, t, p->gbuffer, d_cameras, view_camera_index,

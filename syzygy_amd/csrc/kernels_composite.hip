@@ -18,30 +18,17 @@
 #include "szg_lean.hpp"
 #include "szg_march.hpp"
 #include "szg_pbr.hpp"
+#include "szg_pixel.hpp"
 #include "szg_vec.hpp"
 
-// Two switches over what phase A and phase C do outside the march (profiles/composite_pixel_path.md measures each alone;
-// results are the same with either off):
-//   SZG_COMPOSITE_FRAME_CONSTANTS  what depends on the camera, the atmosphere and the draw extent alone is read from
-//                                  FramePrep::Camera (k_frame_prep, once per frame) instead of being formed per pixel
-//   SZG_COMPOSITE_LEAN_PIXEL       the per-pixel quotients, square roots and pow() of phases A and C use the lean exact operators
-//                                  of szg_lean.hpp where a wave-uniform gate proves their operand domain
-#ifndef SZG_COMPOSITE_FRAME_CONSTANTS
-#define SZG_COMPOSITE_FRAME_CONSTANTS 1
-#endif
-#ifndef SZG_COMPOSITE_LEAN_PIXEL
-#define SZG_COMPOSITE_LEAN_PIXEL 1
-#endif
+// Outside the march, what depends on the camera, the atmosphere and the draw extent alone comes from FramePrep::Camera
+// (k_frame_prep, once per frame), and the per-pixel quotients, square roots and pow() of phases A and C use the lean exact
+// operators of szg_lean.hpp where a wave-uniform gate proves their operand domain (profiles/composite_pixel_path.md).
 
 namespace szg
 {
 namespace
 {
-template <typename T> SZG_DEV T* row_ptr(const szg_image& im, unsigned y)
-{
-    return reinterpret_cast<T*>(static_cast<unsigned char*>(im.data) + (size_t)y * im.pitch_bytes);
-}
-
 struct SkyLut
 {
     const float4* texels;
@@ -181,11 +168,6 @@ struct TailStamp
 };
 #endif
 
-struct GBufferPtrsC
-{
-    szg_image diffuse, specular, normal, position, orm;
-};
-
 // Trilinear fetch of the aerial-perspective luminance volume at screen position (sx, sy) in [0, 1] and distance
 // `dist` (Mm): clamp-to-edge in x, y; slices at d_k = (k + .5) / D * maxDistance, linear ramp to 0 below d_0.
 SZG_DEV V3 sampleAerial(const AerialLut& A, float sx, float sy, float dist)
@@ -202,11 +184,10 @@ SZG_DEV V3 sampleAerial(const AerialLut& A, float sx, float sy, float dist)
     return (l0 * (1.0f - wz) + l1 * wz) * ramp;
 }
 
-#ifndef SZG_COMPOSITE_WAVES
-#define SZG_COMPOSITE_WAVES 4
-#endif
+// waves per SIMD the register budget is held to (tests/test_march_kernel_resources.py pins the occupancy)
+constexpr unsigned COMPOSITE_WAVES = 4u;
 template <bool FAST>
-__global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_image color, szg_image depth, szg_image debug, GBufferPtrsC g,
+__global__ __launch_bounds__(256, COMPOSITE_WAVES) void k_composite(szg_image color, szg_image depth, szg_image debug, GBufferPtrs g,
                                                    unsigned drawW, unsigned drawH, unsigned localRows, RowMap rm,
                                                    ShadowSlot sunSlot, const szg_atmosphere_packed* __restrict__ atmospheres,
                                                    unsigned atmosphereIndex, const szg_camera_packed* __restrict__ cameras,
@@ -217,14 +198,12 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
                                                    const FramePrep* __restrict__ prep)
 {
     unsigned const tid = threadIdx.x;
-    unsigned const wave = tid >> 6, lane = tid & 63u;
+    unsigned const wave = tid >> 6; // (the pixel's column and the diagnostic build's stamp share it)
 #ifdef SZG_TAIL_DIAG
     TailStamp const stamp((blockIdx.y * gridDim.x + blockIdx.x) * 4u + wave);
 #endif
-    unsigned const x = blockIdx.x * 32u + wave * 8u + (lane & 7u);
-    // Workgroups are dispatched in blockIdx order; the rows are walked from the bottom of the image upwards so that the
-    // cheap workgroups (sky: no march) tend to come last and fill the tail of the launch instead of its start.
-    unsigned const y = (gridDim.y - 1u - blockIdx.y) * 8u + (lane >> 3);
+    // (bottom-up: the sky's workgroups, which march nothing, tend to come last and fill the tail of the launch)
+    unsigned const x = pixel_column(wave, tid & 63u), y = pixel_row_bottom_up(tid);
     if (x >= drawW || y >= localRows)
     {
         return;
@@ -240,28 +219,13 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     float const sceneDepth = row_ptr<const float>(depth, y)[x];
 
     // camera.comp:320-322
-#if SZG_COMPOSITE_FRAME_CONSTANTS
     const FramePrep::Camera& fc = prep->camera; // (scalar loads; read in phase A only)
     V3 const position = fc.position;
-#else
-    V3 position = mk3(cam->position[0], cam->position[1], cam->position[2]) / 1000000.0f;
-    position.y *= -1.0f;
-    position.y += a.planetRadius;
-#endif
 
     // camera.comp:324-328 (no pixel-centre offset: SURVEY Q5; global row)
-#if SZG_COMPOSITE_LEAN_PIXEL
     // x and the row are 0 or an integer in [1, 2^32), the extents integers in [1, 2^32): inside the domain of divR0 whatever
     // the frame (no gate), and a zero quotient is +0 as IEEE gives it
-#if SZG_COMPOSITE_FRAME_CONSTANTS
-    float const rcpW = fc.rcpDrawW, rcpH = fc.rcpDrawH;
-#else
-    float const rcpW = rcpN((float)drawW), rcpH = rcpN((float)drawH);
-#endif
-    float const screenx = divR0((float)x, (float)drawW, rcpW), screeny = divR0((float)gy, (float)drawH, rcpH);
-#else
-    float const screenx = (float)x / (float)drawW, screeny = (float)gy / (float)drawH;
-#endif
+    float const screenx = divR0((float)x, (float)drawW, fc.rcpDrawW), screeny = divR0((float)gy, (float)drawH, fc.rcpDrawH);
     float const clipx = (screenx - 0.5f) * 2.0f;
     float const clipy = (screeny - 0.5f) * 2.0f;
     M4 const inverseProjection = load_m4(cam->inverseProjection);
@@ -271,7 +235,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     // normalize() as v * (1 / sqrt(dot)) with the lean operators when every lane's squared length is a moderate number
     V3 const unrotated = mk3(rot.x, rot.y, rot.z);
     float const unrotated2 = dot(unrotated, unrotated);
-    bool const viewLean = SZG_COMPOSITE_LEAN_PIXEL && waveAll(leanLength2(unrotated2));
+    bool const viewLean = waveAll(leanLength2(unrotated2));
     V3 direction = viewLean ? unrotated * divN0(1.0f, sqrtP(unrotated2)) : normalize(unrotated);
     direction.y *= -1.0f;
 
@@ -288,7 +252,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         float4 const p4 = row_ptr<const float4>(g.position, y)[x];
         // (the quotients by max(specular) and by pi and pow(160, .) with the lean operators when no lane of the wave has a black,
         // non-finite or negative-max specular, a non-finite diffuse, or a roughness of 1 or beyond fp32's moderate range)
-        bool const materialLean = SZG_COMPOSITE_LEAN_PIXEL && waveAll(convertPBRLeanOK(diffuse, specular, orm));
+        bool const materialLean = waveAll(convertPBRLeanOK(diffuse, specular, orm));
         m = materialLean ? convertPBR<true>(V4{p4.x, p4.y, p4.z, p4.w}, normal, diffuse, specular, orm)
                          : convertPBR<false>(V4{p4.x, p4.y, p4.z, p4.w}, normal, diffuse, specular, orm);
         isSky = m.position.y > 0.0f; // underground, +y down (:354)
@@ -315,26 +279,17 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         }
         else
         {
-#if SZG_COMPOSITE_FRAME_CONSTANTS
             base = sampleMapDirection(S, fc, direction) + sampleSunDisk(L, a, position, direction, fc.sunLength) * 1.0f;
-#else
-            base = sampleMapDirection(S, a, position, direction) + sampleSunDisk(L, a, position, direction) * 1.0f;
-#endif
         }
     }
     else
     {
         // camera.comp:364
         uint2 const prior = row_ptr<const uint2>(color, y)[x];
-#if SZG_COMPOSITE_LEAN_PIXEL
         // (numerators 0 or an integer in [1, 65535]: inside the domain of divR0 for every texel, no gate)
         float const rcp65535 = rcpN(65535.0f);
         surfaceLuminance = mk3(divR0((float)(prior.x & 0xFFFFu), 65535.0f, rcp65535), divR0((float)(prior.x >> 16), 65535.0f, rcp65535),
                                divR0((float)(prior.y & 0xFFFFu), 65535.0f, rcp65535));
-#else
-        surfaceLuminance = mk3((float)(prior.x & 0xFFFFu) / 65535.0f, (float)(prior.x >> 16) / 65535.0f,
-                               (float)(prior.y & 0xFFFFu) / 65535.0f);
-#endif
 
         // camera.comp:366-369: shadow frame from the engine-space position/normal
         float shadowFactor = 1.0f;
@@ -368,38 +323,24 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         V3 const surfacePosition = m.position;
         // the two transmittance samples of this branch with the lean exact operators when the whole wave allows it
         V3 const toSurface = surfacePosition - position;
-#if SZG_COMPOSITE_FRAME_CONSTANTS
-        float const cameraR2 = fc.r2;
-#else
-        float const cameraR2 = dot(position, position);
-#endif
+        float const cameraR2 = fc.r2; // dot(position, position)
         bool const samplesLean = waveAll(a.lean && leanRadius2(a, cameraR2) && leanRadius2(a, dot(surfacePosition, surfacePosition)) &&
                                          leanLength2(dot(toSurface, toSurface)) &&
                                          leanLength2(dot(a.incidentDirectionSun, a.incidentDirectionSun)));
-#if SZG_COMPOSITE_FRAME_CONSTANTS
         RadiusPart const cameraPart = cameraRadiusPart(fc);
         V3 const transmittanceToSurface = samplesLean ? sampleT_Segment<true>(L, a, position, cameraPart, fc.lenFrom, surfacePosition)
                                                       : sampleT_Segment<false>(L, a, position, cameraPart, fc.lenFrom, surfacePosition);
-#else
-        V3 const transmittanceToSurface = samplesLean ? sampleT_Segment<true>(L, a, position, surfacePosition)
-                                                      : sampleT_Segment<false>(L, a, position, surfacePosition);
-#endif
         // (normalize(), length() and the quotients below likewise: v * (1 / sqrt(dot)) and sqrt(dot) with the lean operators)
         V3 const minusDirection = -direction;
         float const direction2 = dot(minusDirection, minusDirection);
         bool const vectorsLean = samplesLean && waveAll(leanLength2(direction2));
-#if SZG_COMPOSITE_FRAME_CONSTANTS
-        V3 const lightDirection = fc.lightDirection; // normalize(minusSun)
-#else
-        V3 const minusSun = -a.incidentDirectionSun;
-        V3 const lightDirection = vectorsLean ? minusSun * divN0(1.0f, sqrtP(dot(minusSun, minusSun))) : normalize(minusSun);
-#endif
+        V3 const lightDirection = fc.lightDirection; // normalize(-a.incidentDirectionSun)
         V3 const viewDirection = vectorsLean ? minusDirection * divN0(1.0f, sqrtP(direction2)) : normalize(minusDirection);
         float pt0 = 0.0f, pt1 = 0.0f;
         bool const shadowedByPlanet = raySphere(surfacePosition, lightDirection, a.planetRadius, pt0, pt1) && pt0 > 0.0f;
         V3 const halfSum = lightDirection + viewDirection;
         bool const brdfLean = vectorsLean && waveAll(inRange(dot(halfSum, halfSum), 0x1p-40f, 8.0f));
-        V3 const brdf = brdfLean ? brdfMix<true, SZG_COMPOSITE_LEAN_PIXEL != 0>(m, lightDirection, viewDirection)
+        V3 const brdf = brdfLean ? brdfMix<true, true>(m, lightDirection, viewDirection)
                                  : brdfMix<false>(m, lightDirection, viewDirection);
         V3 const transmittanceToSun = samplesLean ? sampleT_Ray<true>(L, a, surfacePosition, lightDirection)
                                                   : sampleT_Ray<false>(L, a, surfacePosition, lightDirection);
@@ -432,11 +373,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
         bool const normalFinite = fabsf(m.normal.x) <= nBig && fabsf(m.normal.y) <= nBig && fabsf(m.normal.z) <= nBig;
         // Both horizon angles asin(Rp / r) must exist: the camera's (every texel of the sky-view LUT depends on it) and the
         // surface's (where the LUT is sampled from); same expressions as skyview_LUT.comp:106-112 and camera.comp:75-77.
-#if SZG_COMPOSITE_FRAME_CONSTANTS
         float const cameraSinHorizon = fc.sinHorizon; // a.planetRadius / length(position)
-#else
-        float const cameraSinHorizon = vectorsLean ? divN0(a.planetRadius, sqrtP(cameraR2)) : a.planetRadius / length(position);
-#endif
         bool const aboveGround = cameraSinHorizon <= 1.0f && fractionOfSunVisible <= 1.0f;
         bool const environmentFinite = a.extModerate && a.sunSane && L.moderate && S.finite && normalFinite && aboveGround &&
                                        inRange(cameraR2, a.extFloor2, a.extCeil2) && inRange(surfaceR2, a.extFloor2, a.extCeil2);
@@ -522,8 +459,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     // through: x, y and the slot addresses of phase A would otherwise wait for it in scratch across the march.
     unsigned tidC = tid;
     asm volatile("" : "+v"(tidC));
-    unsigned const xC = blockIdx.x * 32u + (tidC >> 6) * 8u + (tidC & 7u);
-    unsigned const yC = (gridDim.y - 1u - blockIdx.y) * 8u + ((tidC & 63u) >> 3);
+    unsigned const xC = pixel_column(tidC), yC = pixel_row_bottom_up(tidC);
     unsigned const flags = s_flags[tidC];
     march0 = (flags & 1u) != 0u;
     march1 = (flags & 2u) != 0u;
@@ -548,8 +484,7 @@ __global__ __launch_bounds__(256, SZG_COMPOSITE_WAVES) void k_composite(szg_imag
     V3 const pre = luminance * 10.0f + surfaceLuminance;
     // (pow() without its special cases when every lane's three values are positive normal numbers: a black, denormal, negative or
     // NaN component sends its wave down the generic form)
-    bool const tonemapLean = SZG_COMPOSITE_LEAN_PIXEL &&
-                             waveAll(powLeanOK(pre.x, 1.2f) && powLeanOK(pre.y, 1.2f) && powLeanOK(pre.z, 1.2f));
+    bool const tonemapLean = waveAll(powLeanOK(pre.x, 1.2f) && powLeanOK(pre.y, 1.2f) && powLeanOK(pre.z, 1.2f));
     V3 const out = tonemapLean ? mk3(powLean(pre.x, 1.2f), powLean(pre.y, 1.2f), powLean(pre.z, 1.2f))
                                : mk3(szg_powf(pre.x, 1.2f), szg_powf(pre.y, 1.2f), szg_powf(pre.z, 1.2f));
     row_ptr<uint2>(color, yC)[xC] = pack_unorm16x4(out.x, out.y, out.z, 1.0f);
@@ -564,14 +499,14 @@ hipError_t launch_composite(hipStream_t s, const szg_scene_texture& scene, unsig
                             unsigned camIndex, const szg_directional_light_packed* d_dir, unsigned sunIndex, const float* tlut,
                             unsigned tW, unsigned tH, const float* slut, unsigned sW, unsigned sH, AerialLut aerial, const void* d_prep)
 {
-    unsigned const rows = tile.nranks <= 1u ? drawH : tile.local_rows;
+    unsigned const rows = tile.local_rows;
     if (rows == 0u || drawW == 0u)
     {
         return hipSuccess;
     }
-    dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
+    dim3 const grid = pixel_grid(drawW, rows);
     RowMap const rm{tile.block_rows, tile.rank, tile.nranks};
-    GBufferPtrsC const gp{g.diffuse, g.specular, g.normal, g.worldPosition, g.occlusionRoughnessMetallic};
+    GBufferPtrs const gp = gptrs(g);
     if (aerial.luminance != nullptr)
     {
         hipLaunchKernelGGL(k_composite<true>, grid, dim3(256), 0, s, scene.color, scene.depth, scene.debug_color, gp, drawW, drawH,

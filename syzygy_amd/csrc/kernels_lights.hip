@@ -1,14 +1,9 @@
-// kernels_deferred.hip — G-buffer fill, light-list prep, deferred lights and the
-// multi-GPU row-tile compose copy, for gfx950.
+// kernels_lights.hip — the deferred lights pass for gfx950.
 //
-//   k_gbuffer_fill : output conventions of deferred/offscreen.frag:61-79 with the
-//                    raster state of renderer/pipelines/deferred.cpp:342-392
-//                    (analytic ray cast instead of the fixed-function rasteriser)
 //   k_light_prep   : per-light invariants of deferred/lights.comp:141-161
 //   k_light_tiles  : per 64x64 screen tile, which lights k_lights has to visit
 //   k_lights       : deferred/lights.comp:110-164, fused with the clear of the
 //                    scene colour (deferred.cpp:715-717)
-//   k_compose      : HBM-bound row scatter after the RCCL gather
 
 #include "szg/fpmath.h"
 #include "szg_formats.hpp"
@@ -16,177 +11,11 @@
 #include "szg_lean.hpp"
 #include "szg_light_tiles.hpp"
 #include "szg_pbr.hpp"
+#include "szg_pixel.hpp"
 #include "szg_vec.hpp"
 
 namespace szg
 {
-namespace
-{
-// 256-thread workgroup = 32x8 pixels; each wave an 8x8 patch.
-SZG_DEV void pixel_of_thread(unsigned& x, unsigned& y)
-{
-    unsigned const tid = threadIdx.x;
-    unsigned const wave = tid >> 6, lane = tid & 63u;
-    x = blockIdx.x * 32u + wave * 8u + (lane & 7u);
-    y = blockIdx.y * 8u + (lane >> 3);
-}
-// The same tiling with the rows walked from the bottom of the image upwards (workgroups are dispatched in blockIdx order):
-// the cheap workgroups - background texels, at the top of most frames - then come last and fill the tail of the launch.
-SZG_DEV void pixel_of_thread_bottom_up(unsigned& x, unsigned& y)
-{
-    unsigned const tid = threadIdx.x;
-    unsigned const wave = tid >> 6, lane = tid & 63u;
-    x = blockIdx.x * 32u + wave * 8u + (lane & 7u);
-    y = (gridDim.y - 1u - blockIdx.y) * 8u + (lane >> 3);
-}
-
-template <typename T> SZG_DEV T* row_ptr(const szg_image& im, unsigned y)
-{
-    return reinterpret_cast<T*>(static_cast<unsigned char*>(im.data) + (size_t)y * im.pitch_bytes);
-}
-} // namespace
-
-struct GBufferPtrs
-{
-    szg_image diffuse, specular, normal, position, orm;
-};
-
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gbuffer_fill(szg_image depth, GBufferPtrs g, unsigned drawW, unsigned drawH,
-                                                      unsigned localRows, RowMap rm,
-                                                      const szg_camera_packed* __restrict__ cameras, unsigned cameraIndex,
-                                                      float ground_y, float ground_half_extent, float checker_cell,
-                                                      float ground_roughness, const szg_fill_box* __restrict__ boxes,
-                                                      unsigned boxCount)
-{
-    unsigned x, y;
-    pixel_of_thread(x, y);
-    if (x >= drawW || y >= localRows)
-    {
-        return;
-    }
-    unsigned const gy = global_row(rm, y);
-    const szg_camera_packed* cam = cameras + cameraIndex;
-    M4 const inverseProjection = load_m4(cam->inverseProjection);
-    M4 const rotation = load_m4(cam->rotation);
-    V3 const origin = mk3(cam->position[0], cam->position[1], cam->position[2]);
-
-    float const ndcx = (((float)x + 0.5f) / (float)drawW - 0.5f) * 2.0f;
-    float const ndcy = (((float)gy + 0.5f) / (float)drawH - 0.5f) * 2.0f;
-    V4 const dv = mul(inverseProjection, ndcx, ndcy, 1.0f, 1.0f);
-    V4 const dw = mul(rotation, dv.x, dv.y, dv.z, dv.w);
-    V3 const dir = normalize(mk3(dw.x, dw.y, dw.z));
-
-    float best_t = 3.0e38f;
-    V3 best_n = splat(0.0f);
-    float best_metallic = 0.0f, best_roughness = 0.0f;
-    bool hit = false;
-
-    if (dir.y != 0.0f)
-    {
-        float const t = (ground_y - origin.y) / dir.y;
-        if (t > 0.0f)
-        {
-            V3 const p = origin + t * dir;
-            if (fabsf(p.x) <= ground_half_extent && fabsf(p.z) <= ground_half_extent && t < best_t)
-            {
-                best_t = t;
-                best_n = mk3(0.0f, -1.0f, 0.0f);
-                best_metallic = 0.0f;
-                best_roughness = ground_roughness;
-                hit = true;
-            }
-        }
-    }
-    float const o[3] = {origin.x, origin.y, origin.z};
-    float const d[3] = {dir.x, dir.y, dir.z};
-    for (unsigned b = 0; b < boxCount; b++)
-    {
-        szg_fill_box const box = boxes[b];
-        float tmin = -3.0e38f, tmax = 3.0e38f;
-        int axis_min = 0;
-        float sign_min = 0.0f;
-        bool miss = false;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++)
-        {
-            float const lo = box.center[ax] - box.half_extent[ax];
-            float const hi = box.center[ax] + box.half_extent[ax];
-            if (d[ax] == 0.0f)
-            {
-                if (o[ax] < lo || o[ax] > hi)
-                {
-                    miss = true;
-                }
-                continue;
-            }
-            float t0 = (lo - o[ax]) / d[ax];
-            float t1 = (hi - o[ax]) / d[ax];
-            float s = -1.0f;
-            if (t0 > t1)
-            {
-                float const tmp = t0;
-                t0 = t1;
-                t1 = tmp;
-                s = 1.0f;
-            }
-            if (t0 > tmin)
-            {
-                tmin = t0;
-                axis_min = ax;
-                sign_min = s;
-            }
-            if (t1 < tmax)
-            {
-                tmax = t1;
-            }
-        }
-        if (miss || tmin > tmax || tmin <= 0.0f)
-        {
-            continue;
-        }
-        if (tmin < best_t)
-        {
-            best_t = tmin;
-            best_n = mk3(axis_min == 0 ? sign_min : 0.0f, axis_min == 1 ? sign_min : 0.0f, axis_min == 2 ? sign_min : 0.0f);
-            best_metallic = box.metallic;
-            best_roughness = box.roughness;
-            hit = true;
-        }
-    }
-
-    float depthOut = 0.0f;
-    float4 pos4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    uint2 nrm = pack_half4(0.0f, 0.0f, 0.0f, 0.0f), dif = nrm, orm = nrm;
-    if (hit)
-    {
-        V3 const p = origin + best_t * dir;
-        M4 const projection = load_m4(cam->projection);
-        M4 const view = load_m4(cam->view);
-        V4 const pv = mul(view, p.x, p.y, p.z, 1.0f);
-        V4 const clip = mul(projection, pv.x, pv.y, pv.z, pv.w);
-        float const dz = clip.z / clip.w;
-        if (dz > 0.0f && dz <= 1.0f)
-        {
-            depthOut = dz;
-            float const cx = floorf(p.x / checker_cell), cy = floorf(p.y / checker_cell), cz = floorf(p.z / checker_cell);
-            float const s = cx + cy + cz;
-            bool const light = (s - 2.0f * floorf(s * 0.5f)) == 0.0f;
-            float const grey = light ? (200.0f / 255.0f) : (100.0f / 255.0f);
-            pos4 = make_float4(p.x, p.y, p.z, 1.0f);
-            nrm = pack_half4(best_n.x, best_n.y, best_n.z, 0.0f);
-            dif = pack_half4(grey, grey, grey, 1.0f);
-            orm = pack_half4(1.0f, best_roughness, best_metallic, 1.0f);
-        }
-    }
-    row_ptr<uint2>(g.diffuse, y)[x] = dif;
-    row_ptr<uint2>(g.specular, y)[x] = dif;
-    row_ptr<uint2>(g.normal, y)[x] = nrm;
-    row_ptr<uint2>(g.orm, y)[x] = orm;
-    row_ptr<float4>(g.position, y)[x] = pos4;
-    row_ptr<float>(depth, y)[x] = depthOut;
-}
-
 // ---------------------------------------------------------------------------
 // One thread per light. Slot numbering follows lights.comp:138-161: the shadow
 // map index starts at directionalLightSkipCount and runs over the directional
@@ -688,12 +517,13 @@ __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image de
         // The optimistic pass (lightContribution<true>): every pixel of the wave finite and within 4096 units of the origin.
         bool const tightPixel = pixelFinite && fabsf(m.position.x) <= 0x1p12f && fabsf(m.position.y) <= 0x1p12f && fabsf(m.position.z) <= 0x1p12f &&
                                 inRange(fabsf(m.specularPower), 0x1p-100f, 0x1p20f); // (the exponent half of powLeanOK)
-        // The workgroup's 32 x 8 pixels lie in one 64 x 64 tile: its mask words are found from blockIdx alone (the row
-        // mapping of pixel_of_thread_bottom_up), in scalar registers.
+        // The workgroup's 32 x 8 pixels lie in one 64 x 64 tile: its mask words are found from the workgroup's first column
+        // and first row (pixel_row_bottom_up's, szg_pixel.hpp) alone, in scalar registers.
         const unsigned long long* tileWords = nullptr;
         if (tileMasks != nullptr)
         {
-            unsigned const tileX = (blockIdx.x * 32u) / LIGHT_TILE_DIM, tileY = ((gridDim.y - 1u - blockIdx.y) * 8u) / LIGHT_TILE_DIM;
+            unsigned const tileX = (blockIdx.x * PIXEL_GROUP_W) / LIGHT_TILE_DIM;
+            unsigned const tileY = (pixel_group_bottom_up() * PIXEL_GROUP_H) / LIGHT_TILE_DIM;
             unsigned const batches = (lightCount + LIGHT_TILE_BATCH - 1u) / LIGHT_TILE_BATCH;
             tileWords = tileMasks + (size_t)(tileY * tilesX + tileX) * batches;
         }
@@ -718,234 +548,6 @@ __global__ __launch_bounds__(256, 6) void k_lights(szg_image color, szg_image de
 }
 
 // ---------------------------------------------------------------------------
-// Row scatter after the gather: rank r's packed tile holds its rows in local
-// order; local row l of rank r is global row ((l / B) * N + r) * B + l % B.
-// 16 B per lane, fully coalesced both sides.
-__global__ __launch_bounds__(256) void k_compose(const uint4* __restrict__ gathered, size_t tileStrideVec, unsigned nranks,
-                                                 unsigned blockRows, unsigned char* __restrict__ dst, unsigned dstPitch,
-                                                 unsigned rowVecs, unsigned height)
-{
-    unsigned const gy = blockIdx.y;
-    unsigned const blk = gy / blockRows;
-    unsigned const rank = blk % nranks;
-    unsigned const local = (blk / nranks) * blockRows + gy % blockRows;
-    const uint4* src = gathered + (size_t)rank * tileStrideVec + (size_t)local * rowVecs;
-    uint4* out = reinterpret_cast<uint4*>(dst + (size_t)gy * dstPitch);
-    for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < rowVecs; v += gridDim.x * 256u)
-    {
-        out[v] = src[v];
-    }
-    (void)height;
-}
-
-// ---------------------------------------------------------------------------
-// Shadow-map generation for the analytic scene (abi.h szg_deferred_record_shadow_maps).
-__global__ void k_shadow_prep(const szg_directional_light_packed* __restrict__ dirs, unsigned dirCount,
-                              const szg_spot_light_packed* __restrict__ spots, unsigned spotCount,
-                              const ShadowSlot* __restrict__ owned, unsigned slotCount, ShadowGen* __restrict__ gen)
-{
-    unsigned const i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= slotCount)
-    {
-        return;
-    }
-    ShadowGen g;
-    g.map = nullptr;
-    g.dim = g.pitchFloats = g.pad = 0u;
-    M4 pv;
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-    {
-        pv.m[k] = 0.0f;
-    }
-    if (i < dirCount + spotCount && owned[i].map != nullptr)
-    {
-        // light.projection * light.view (shadowpass.cpp:207-215)
-        // (a host-side product in the reference: glm semantics, not the shaders' contraction rule)
-        pv = (i < dirCount) ? mulGlm(load_m4(dirs[i].projection), load_m4(dirs[i].view))
-                            : mulGlm(load_m4(spots[i - dirCount].projection), load_m4(spots[i - dirCount].view));
-        g.map = const_cast<float*>(owned[i].map);
-        g.dim = owned[i].width;
-        g.pitchFloats = owned[i].pitchFloats;
-    }
-    M4 const inv = inverse4(pv);
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-    {
-        g.projView[k] = pv.m[k];
-        g.invProjView[k] = inv.m[k];
-    }
-    gen[i] = g;
-}
-
-__global__ __launch_bounds__(256) void k_shadow_fill(const ShadowGen* __restrict__ gen, const szg_fill_box* __restrict__ boxes,
-                                                     unsigned boxCount)
-{
-    const ShadowGen* G = gen + blockIdx.z;
-    if (G->map == nullptr)
-    {
-        return;
-    }
-    unsigned x, y;
-    pixel_of_thread(x, y);
-    unsigned const dim = G->dim;
-    if (x >= dim || y >= dim)
-    {
-        return;
-    }
-    M4 pv, inv;
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-    {
-        pv.m[k] = G->projView[k];
-        inv.m[k] = G->invProjView[k];
-    }
-    // texel centre -> NDC (inverse of TO_TEX_COORD_MAT, shadowmap.glinl:2-7): s = 0.5 ndc + 0.5
-    float const ndcx = (((float)x + 0.5f) / (float)dim) * 2.0f - 1.0f;
-    float const ndcy = (((float)y + 0.5f) / (float)dim) * 2.0f - 1.0f;
-    V4 const h1 = mul(inv, ndcx, ndcy, 1.0f, 1.0f); // reverse-Z: depth 1 = near plane
-    V4 const h2 = mul(inv, ndcx, ndcy, 0.5f, 1.0f);
-    V3 const p1 = mk3(h1.x / h1.w, h1.y / h1.w, h1.z / h1.w);
-    V3 const p2 = mk3(h2.x / h2.w, h2.y / h2.w, h2.z / h2.w);
-    V3 const dir = normalize(p2 - p1);
-    float const o[3] = {p1.x, p1.y, p1.z};
-    float const d[3] = {dir.x, dir.y, dir.z};
-    float best = 0.0f; // cleared depth = far
-    for (unsigned b = 0; b < boxCount; b++)
-    {
-        szg_fill_box const box = boxes[b];
-        float tmin = -3.0e38f, tmax = 3.0e38f;
-        bool miss = false;
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++)
-        {
-            float const lo = box.center[ax] - box.half_extent[ax];
-            float const hi = box.center[ax] + box.half_extent[ax];
-            if (d[ax] == 0.0f)
-            {
-                if (o[ax] < lo || o[ax] > hi)
-                {
-                    miss = true;
-                }
-                continue;
-            }
-            float t0 = (lo - o[ax]) / d[ax];
-            float t1 = (hi - o[ax]) / d[ax];
-            if (t0 > t1)
-            {
-                float const tmp = t0;
-                t0 = t1;
-                t1 = tmp;
-            }
-            tmin = fmaxf(tmin, t0);
-            tmax = fminf(tmax, t1);
-        }
-        if (miss || tmin > tmax || tmax <= 0.0f)
-        {
-            continue;
-        }
-        V3 const pe = p1 + tmax * dir; // back face: what front-face culling leaves (pipelines.cpp:656-659)
-        V4 const clip = mul(pv, pe.x, pe.y, pe.z, 1.0f);
-        float const depth = clip.z / clip.w;
-        if (depth > 0.0f && depth <= 1.0f && depth >= best) // GREATER_OR_EQUAL (pipelines.cpp:661)
-        {
-            best = depth;
-        }
-    }
-    G->map[(size_t)y * G->pitchFloats + x] = best;
-}
-
-// ---------------------------------------------------------------------------
-// transfer/oetf_srgb.comp:9-19, transfer/oetf_pure_gamma.comp:9 — in place on RGBA16 UNORM. Two pixels (16 B)
-// per lane per access, fully coalesced; 16 B/px of traffic.
-SZG_DEV float oetf(float linear, unsigned function)
-{
-    if (function == SZG_OETF_SRGB)
-    {
-        float const lower = 12.92f * linear;
-        float const higher = szg_powf(linear, (float)(1.0 / 2.4)) * 1.055f - 0.055f;
-        return (linear <= 0.0031308f) ? lower : higher; // mix(higher, lower, cutoff)
-    }
-    // (float)(1.0 / 2.2), not 1.0f / 2.2f: the constant of the reference's SPIR-V, folded in double (oracle_oetf)
-    return szg_powf(linear, (float)(1.0 / 2.2));
-}
-SZG_DEV unsigned oetf_pair(unsigned packed, unsigned function, bool hiIsAlpha)
-{
-    float const a = (float)(packed & 0xFFFFu) / 65535.0f;
-    float const b = (float)(packed >> 16) / 65535.0f;
-    unsigned const lo = unorm16(oetf(a, function));
-    unsigned const hi = hiIsAlpha ? (packed >> 16) : unorm16(oetf(b, function));
-    return lo | (hi << 16);
-}
-// The OETF is a pure function of a 16-bit channel value: 65 536 possible inputs. k_oetf_table evaluates the
-// expression above once per input; k_oetf then maps every channel through the 128 KiB table (L2-resident gathers),
-// which leaves the pass with ~20 instructions per pixel against 16 B of traffic: HBM-bound, and bit-identical to
-// evaluating the three pow() per pixel.
-__global__ __launch_bounds__(256) void k_oetf_table(unsigned short* __restrict__ table, unsigned function)
-{
-    unsigned const i = blockIdx.x * 256u + threadIdx.x; // 256 x 256 threads
-    table[i] = (unsigned short)unorm16(oetf((float)i / 65535.0f, function));
-}
-SZG_DEV unsigned oetf_pair_lut(unsigned packed, const unsigned short* __restrict__ table, bool hiIsAlpha)
-{
-    unsigned const lo = table[packed & 0xFFFFu];
-    unsigned const hi = hiIsAlpha ? (packed >> 16) : (unsigned)table[packed >> 16];
-    return lo | (hi << 16);
-}
-__global__ __launch_bounds__(256) void k_oetf(unsigned char* __restrict__ data, unsigned pitch, unsigned width, unsigned height,
-                                             const unsigned short* __restrict__ table)
-{
-    unsigned const pairs = (width + 1u) / 2u; // uint4 = 2 pixels
-    for (unsigned y = blockIdx.y; y < height; y += gridDim.y)
-    {
-        uint4* row = reinterpret_cast<uint4*>(data + (size_t)y * pitch);
-        for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < pairs; v += gridDim.x * 256u)
-        {
-            if (2u * v + 1u < width)
-            {
-                uint4 t = row[v];
-                t.x = oetf_pair_lut(t.x, table, false);
-                t.y = oetf_pair_lut(t.y, table, true);
-                t.z = oetf_pair_lut(t.z, table, false);
-                t.w = oetf_pair_lut(t.w, table, true);
-                row[v] = t;
-            }
-            else
-            {
-                uint2* px = reinterpret_cast<uint2*>(row) + 2u * v; // odd width: last single pixel
-                uint2 t = *px;
-                t.x = oetf_pair_lut(t.x, table, false);
-                t.y = oetf_pair_lut(t.y, table, true);
-                *px = t;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-static GBufferPtrs gptrs(const szg_gbuffer& g)
-{
-    return GBufferPtrs{g.diffuse, g.specular, g.normal, g.worldPosition, g.occlusionRoughnessMetallic};
-}
-static unsigned local_rows_of(const TileArgs& t, unsigned drawH) { return t.nranks <= 1u ? drawH : t.local_rows; }
-
-hipError_t launch_gbuffer_fill(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
-                               const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, float ground_y,
-                               float ground_half_extent, float checker_cell, float ground_roughness,
-                               const szg_fill_box* d_boxes, unsigned boxCount)
-{
-    unsigned const rows = local_rows_of(tile, drawH);
-    if (rows == 0u || drawW == 0u)
-    {
-        return hipSuccess;
-    }
-    dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
-    RowMap const rm{tile.block_rows, tile.rank, tile.nranks};
-    hipLaunchKernelGGL(k_gbuffer_fill, grid, dim3(256), 0, s, scene.depth, gptrs(g), drawW, drawH, rows, rm, d_cam, camIndex,
-                       ground_y, ground_half_extent, checker_cell, ground_roughness, d_boxes, boxCount);
-    return hipGetLastError();
-}
-
 hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount, unsigned dirSkip,
                              const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_slots,
                              unsigned slotCount, LightRec* d_out)
@@ -965,13 +567,12 @@ hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned
                          const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, const LightRec* d_lights,
                          unsigned lightCount, const unsigned long long* d_tileMasks)
 {
-    unsigned const rows = local_rows_of(tile, drawH);
+    unsigned const rows = tile.local_rows;
     if (rows == 0u || drawW == 0u)
     {
         return hipSuccess;
     }
-    dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
-    hipLaunchKernelGGL(k_lights, grid, dim3(256), 0, s, scene.color, scene.debug_color, gptrs(g), drawW, rows, d_cam, camIndex,
+    hipLaunchKernelGGL(k_lights, pixel_grid(drawW, rows), dim3(256), 0, s, scene.color, scene.debug_color, gptrs(g), drawW, rows, d_cam, camIndex,
                        d_lights, lightCount, d_tileMasks, (drawW + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM);
     return hipGetLastError();
 }
@@ -979,78 +580,13 @@ hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned
 hipError_t launch_light_tiles(hipStream_t s, unsigned drawW, unsigned drawH, TileArgs tile, const szg_gbuffer& g,
                               const LightRec* d_lights, unsigned lightCount, unsigned long long* d_tileMasks)
 {
-    unsigned const rows = local_rows_of(tile, drawH);
+    unsigned const rows = tile.local_rows;
     if (rows == 0u || drawW == 0u || lightCount == 0u)
     {
         return hipSuccess;
     }
     dim3 const grid((drawW + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM, (rows + LIGHT_TILE_DIM - 1u) / LIGHT_TILE_DIM);
     hipLaunchKernelGGL(k_light_tiles, grid, dim3(256), 0, s, g.worldPosition, drawW, rows, d_lights, lightCount, d_tileMasks);
-    return hipGetLastError();
-}
-
-hipError_t launch_shadow_maps(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount,
-                              const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_ownedSlots,
-                              unsigned slotCount, ShadowGen* d_gen, const szg_fill_box* d_boxes, unsigned boxCount, unsigned maxDim)
-{
-    if (slotCount == 0u || maxDim == 0u)
-    {
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(k_shadow_prep, dim3((slotCount + 63u) / 64u), dim3(64), 0, s, d_dir, dirCount, d_spot, spotCount, d_ownedSlots,
-                       slotCount, d_gen);
-    hipLaunchKernelGGL(k_shadow_fill, dim3((maxDim + 31u) / 32u, (maxDim + 7u) / 8u, slotCount), dim3(256), 0, s, d_gen, d_boxes,
-                       boxCount);
-    return hipGetLastError();
-}
-
-hipError_t launch_shadow_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount,
-                              const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_ownedSlots,
-                              unsigned slotCount, ShadowGen* d_gen)
-{
-    if (slotCount == 0u)
-    {
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(k_shadow_prep, dim3((slotCount + 63u) / 64u), dim3(64), 0, s, d_dir, dirCount, d_spot, spotCount, d_ownedSlots,
-                       slotCount, d_gen);
-    return hipGetLastError();
-}
-
-hipError_t launch_oetf_table(hipStream_t s, unsigned short* table, unsigned function)
-{
-    hipLaunchKernelGGL(k_oetf_table, dim3(256), dim3(256), 0, s, table, function);
-    return hipGetLastError();
-}
-
-hipError_t launch_oetf(hipStream_t s, const szg_image& image, unsigned width, unsigned height, const unsigned short* table)
-{
-    if (width == 0u || height == 0u)
-    {
-        return hipSuccess;
-    }
-    unsigned const pairs = (width + 1u) / 2u;
-    unsigned gx = (pairs + 255u) / 256u;
-    gx = gx > 8u ? 8u : gx;
-    unsigned const gy = height > 65535u ? 65535u : height;
-    hipLaunchKernelGGL(k_oetf, dim3(gx, gy), dim3(256), 0, s, static_cast<unsigned char*>(image.data), image.pitch_bytes, width, height,
-                       table);
-    return hipGetLastError();
-}
-
-hipError_t launch_compose_rowtiles(hipStream_t s, const void* gathered, size_t tileStrideBytes, unsigned nranks,
-                                   unsigned blockRows, const szg_image& dst, unsigned width, unsigned height)
-{
-    if (width == 0u || height == 0u)
-    {
-        return hipSuccess;
-    }
-    unsigned const rowBytes = width * 8u; // RGBA16_UNORM
-    unsigned const rowVecs = rowBytes / 16u;
-    unsigned const gx = (rowVecs + 255u) / 256u;
-    hipLaunchKernelGGL(k_compose, dim3(gx > 8u ? 8u : gx, height), dim3(256), 0, s, static_cast<const uint4*>(gathered),
-                       tileStrideBytes / 16u, nranks, blockRows, static_cast<unsigned char*>(dst.data), dst.pitch_bytes, rowVecs,
-                       height);
     return hipGetLastError();
 }
 } // namespace szg

@@ -17,6 +17,7 @@
 #include "szg/exact_sign.h"
 #include "szg_formats.hpp"
 #include "szg_launch.hpp"
+#include "szg_pixel.hpp"
 #include "szg_texture.hpp"
 #include "szg_vec.hpp"
 
@@ -24,11 +25,6 @@ namespace szg
 {
 namespace
 {
-template <typename T> SZG_DEV T* row_ptr(const szg_image& im, unsigned y)
-{
-    return reinterpret_cast<T*>(static_cast<unsigned char*>(im.data) + (size_t)y * im.pitch_bytes);
-}
-
 SZG_DEV V3 cross3(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 // submission-order primitive -> (draw, instance, triangle): draws are sorted by firstPrim
@@ -740,12 +736,12 @@ hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, uns
                               const szg_gbuffer& g, const RasterDraw* d_draws, const RasterBuffers& b, unsigned primCount,
                               const szg_camera_packed* d_cam, unsigned camIndex, bool mips, bool aniso)
 {
-    unsigned const rows = tile.nranks <= 1u ? drawH : tile.local_rows;
+    unsigned const rows = tile.local_rows;
     if (rows == 0u || drawW == 0u)
     {
         return hipSuccess;
     }
-    dim3 const grid((drawW + 31u) / 32u, (rows + 7u) / 8u);
+    dim3 const grid = pixel_grid(drawW, rows);
     RowMap const rm{tile.block_rows, tile.rank, tile.nranks};
     if (mips && aniso)
     {
@@ -772,8 +768,8 @@ hipError_t launch_shadow_tile(hipStream_t s, const ShadowGen* d_gen, unsigned di
     {
         return hipSuccess;
     }
-    hipLaunchKernelGGL(k_shadow_tile, dim3((dim + 31u) / 32u, (dim + 7u) / 8u), dim3(256), 0, s, d_gen, b.prims, hierarchyOf(b, primCount),
-                       biasConstant, biasSlope);
+    hipLaunchKernelGGL(k_shadow_tile, pixel_grid(dim, dim), dim3(256), 0, s, d_gen, b.prims, hierarchyOf(b, primCount), biasConstant,
+                       biasSlope);
     return hipGetLastError();
 }
 } // namespace szg

@@ -26,7 +26,7 @@ SZG_DEV V4 unpack_unorm16x4(uint2 t)
     return V4{unorm16_to_float(t.x & 0xFFFFu), unorm16_to_float(t.x >> 16), unorm16_to_float(t.y & 0xFFFFu), unorm16_to_float(t.y >> 16)};
 }
 
-// SZG_OETF_SRGB of szg_record_oetf. The expression lives in two places: here and in oetf() of kernels_deferred.hip.
+// SZG_OETF_SRGB of szg_record_oetf (transfer/oetf_srgb.comp:9-19); kernels_oetf.hip evaluates it through this function too.
 SZG_DEV float encode_srgb(float linear)
 {
     float const lower = 12.92f * linear;

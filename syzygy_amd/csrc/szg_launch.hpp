@@ -32,7 +32,7 @@ struct LightRec
     // (bit 0 also says: the light's own factors are finite and non-zero where they divide, so a culled pixel's term is an exact 0)
     // bit 1 (implies bit 0), "tight": |position| <= 2^12, |shadow rows| <= 2^14 and falloffBound in [2^-20, 2^20]. Together with
     // pixel positions <= 2^12 this bounds every operand of the lean ops from ABOVE by construction (|clip| < 2^28, d^2 < 2^28,
-    // falloff < 2^48), so that k_lights' optimistic pass only has to track their LOWER bounds (kernels_deferred.hip).
+    // falloff < 2^48), so that k_lights' optimistic pass only has to track their LOWER bounds (kernels_lights.hip).
     float falloffBound;       // falloffFactor / falloffDistance^2 when leanOK: falloffBound * d^2 ~ the light's falloff at distance d
     float rcpFalloffDistance; // rcpN(falloffDistance) when leanOK: the shared reciprocal of dist / falloffDistance (once per light, not per wave)
 };
@@ -53,6 +53,8 @@ struct AerialLut
     float maxDistance;
 };
 
+// The rows of a draw that this rank owns (szg_rowtile), as resolve_tile (api_core.cpp) hands them to every launch function.
+// `local_rows` is the number of rows this rank draws; resolve_tile sets it to the draw height for a single rank.
 struct TileArgs
 {
     unsigned block_rows, rank, nranks, local_rows;
@@ -102,6 +104,17 @@ size_t frame_prep_bytes();
 hipError_t launch_frame_prep(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, unsigned tW, unsigned tH, void* d_prep,
                              const szg_directional_light_packed* d_sun = nullptr, const szg_camera_packed* d_cam = nullptr,
                              unsigned camIndex = 0u, unsigned drawW = 0u, unsigned drawH = 0u);
+hipError_t launch_composite(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
+                            const szg_gbuffer& g, ShadowSlot sunSlot, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const szg_camera_packed* d_cam,
+                            unsigned camIndex, const szg_directional_light_packed* d_dir, unsigned sunIndex, const float* tlut,
+                            unsigned tW, unsigned tH, const float* slut, unsigned sW, unsigned sH, AerialLut aerial, const void* d_prep);
+hipError_t launch_aerial_lut(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const szg_camera_packed* d_cam,
+                             unsigned camIndex, const float* tlut, unsigned tW, unsigned tH, float* luminance, float* transmittance,
+                             unsigned W, unsigned H, unsigned D, float maxDistance);
+hipError_t launch_multiscatter(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const float* tlut, unsigned tW,
+                               unsigned tH, float* out, unsigned dim);
+
+// ---- deferred lights pass (kernels_lights.hip) ----
 hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount, unsigned dirSkip,
                              const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_slots,
                              unsigned slotCount, LightRec* d_out);
@@ -113,19 +126,12 @@ hipError_t launch_lights(hipStream_t s, const szg_scene_texture& scene, unsigned
 // is handed them (nullptr: every light is visited).
 hipError_t launch_light_tiles(hipStream_t s, unsigned drawW, unsigned drawH, TileArgs tile, const szg_gbuffer& g,
                               const LightRec* d_lights, unsigned lightCount, unsigned long long* d_tileMasks);
+
+// ---- analytic scene: G-buffer fill and shadow maps (kernels_scene_fill.hip) ----
 hipError_t launch_gbuffer_fill(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
                                const szg_gbuffer& g, const szg_camera_packed* d_cam, unsigned camIndex, float ground_y,
                                float ground_half_extent, float checker_cell, float ground_roughness,
                                const szg_fill_box* d_boxes, unsigned boxCount);
-hipError_t launch_composite(hipStream_t s, const szg_scene_texture& scene, unsigned drawW, unsigned drawH, TileArgs tile,
-                            const szg_gbuffer& g, ShadowSlot sunSlot, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const szg_camera_packed* d_cam,
-                            unsigned camIndex, const szg_directional_light_packed* d_dir, unsigned sunIndex, const float* tlut,
-                            unsigned tW, unsigned tH, const float* slut, unsigned sW, unsigned sH, AerialLut aerial, const void* d_prep);
-hipError_t launch_aerial_lut(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const szg_camera_packed* d_cam,
-                             unsigned camIndex, const float* tlut, unsigned tW, unsigned tH, float* luminance, float* transmittance,
-                             unsigned W, unsigned H, unsigned D, float maxDistance);
-hipError_t launch_multiscatter(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const float* tlut, unsigned tW,
-                               unsigned tH, float* out, unsigned dim);
 // Per-slot state for shadow-map generation, built on the device by k_shadow_prep.
 struct ShadowGen
 {
@@ -140,6 +146,15 @@ hipError_t launch_shadow_maps(hipStream_t s, const szg_directional_light_packed*
 hipError_t launch_shadow_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount,
                               const szg_spot_light_packed* d_spot, unsigned spotCount, const ShadowSlot* d_ownedSlots,
                               unsigned slotCount, ShadowGen* d_gen);
+
+// ---- OETF pass (kernels_oetf.hip) ----
+// `table`: 65536 x u16, the OETF of every UNORM16 channel value (launch_oetf_table fills it)
+hipError_t launch_oetf_table(hipStream_t s, unsigned short* table, unsigned function);
+hipError_t launch_oetf(hipStream_t s, const szg_image& image, unsigned width, unsigned height, const unsigned short* table);
+
+// ---- multi-GPU row-tile compose copy (kernels_rowtile.hip) ----
+hipError_t launch_compose_rowtiles(hipStream_t s, const void* gathered, size_t tileStrideBytes, unsigned nranks,
+                                   unsigned blockRows, const szg_image& dst, unsigned width, unsigned height);
 
 // ---- compute rasteriser (kernels_raster.hip, include/szg/raster.h) ----
 // One vkCmdDrawIndexed of the reference (one surface of one mesh, all its instances), uploaded by the host.
@@ -208,11 +223,6 @@ hipError_t launch_raster_tile(hipStream_t s, const szg_scene_texture& scene, uns
 hipError_t launch_generate_mipmaps(hipStream_t s, const szg_texture& level0, void* d_chain);
 hipError_t launch_shadow_tile(hipStream_t s, const ShadowGen* d_gen, unsigned dim, const RasterBuffers& b, unsigned primCount,
                               float biasConstant, float biasSlope);
-// `table`: 65536 x u16, the OETF of every UNORM16 channel value (launch_oetf_table fills it)
-hipError_t launch_oetf_table(hipStream_t s, unsigned short* table, unsigned function);
-hipError_t launch_oetf(hipStream_t s, const szg_image& image, unsigned width, unsigned height, const unsigned short* table);
-hipError_t launch_compose_rowtiles(hipStream_t s, const void* gathered, size_t tileStrideBytes, unsigned nranks,
-                                   unsigned blockRows, const szg_image& dst, unsigned width, unsigned height);
 
 // ---- debug-line pass (kernels_debuglines.hip, include/szg/debuglines.h) ----
 // One line after setup: viewport endpoints, the coverage terms of the header, and its major-axis pixel range.

@@ -36,7 +36,7 @@ struct LightCull
 // One pair's cull: rows x, y and w of shadowMatrix * vec4(p, 1), each summed left to right as the shader does, the squared
 // distance to the light, and `skip`: the light is a spot light whose record says its own factors are finite (`flags` bit 0 of
 // LightRec::leanOK), falloffBound * d^2 >= 2^-28, and the position surely lies outside the cone. (The caller may act on `skip`
-// only where every pixel of its wave is finite, kernels_deferred.hip.)
+// only where every pixel of its wave is finite, kernels_lights.hip.)
 struct PairCull
 {
     float cx, cy, cw, d2;

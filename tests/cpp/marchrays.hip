@@ -1,4 +1,4 @@
-// marchrays.hip — test infrastructure: scatteringIntegral / marchLoop of syzygy_amd/csrc/szg_device.hpp called RAY BY RAY on
+// marchrays.hip — test infrastructure: scatteringIntegral / marchLoop of syzygy_amd/csrc/szg_march.hpp called RAY BY RAY on
 // the GPU, one thread per ray, so that a test decides which rays share a wave (tests/march_rays.py lays the waves out,
 // tests/test_gpu_march_rays.py compares every lane with the oracle's scalar march bit for bit). Built with the product's
 // HIPFLAGS (tests/Makefile; the flag line is checked by tests/test_device_arith_build.py).
@@ -15,7 +15,7 @@
 
 #include <cstdint>
 
-#include "kernels_lut.hip" // (found on the include path, like the szg_device.hpp it includes)
+#include "kernels_lut.hip" // (found on the include path, like the szg_*.hpp device headers it includes)
 
 namespace
 {

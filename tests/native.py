@@ -4,6 +4,7 @@ import fcntl
 import glob
 import hashlib
 import os
+import re
 import subprocess
 
 from __graft_entry__ import source_hash
@@ -55,6 +56,16 @@ def build(target, directory=TESTS, hashed=None):
             with open(stamp, "w") as f:
                 f.write(want + "\n")
     return artefact
+
+
+def assignments(path):
+    """name -> (operator, value) of the variable assignments of a Makefile (no continuation lines in these files)."""
+    out = {}
+    for line in open(path):
+        m = re.match(r"^([A-Za-z_][A-Za-z0-9_]*)\s*(\?=|:=|=)\s*(.*?)\s*$", line)
+        if m:
+            out[m.group(1)] = (m.group(2), m.group(3))
+    return out
 
 
 def commands(target, directory=TESTS):

@@ -14,19 +14,9 @@ LIBRARIES = ("cpp/libszg_devarith.so", "cpp/libszg_marchrays.so", "mipsample/lib
 LITERAL_LIBRARIES = {"cpp/libszg_marchrays_literal.so": "cpp/libszg_marchrays.so"}  # literal target -> the plain one of the same source
 
 
-def _assignments(path):
-    """name -> (operator, value) of the variable assignments of a Makefile (no continuation lines in these files)."""
-    out = {}
-    for line in open(path):
-        m = re.match(r"^([A-Za-z_][A-Za-z0-9_]*)\s*(\?=|:=|=)\s*(.*?)\s*$", line)
-        if m:
-            out[m.group(1)] = (m.group(2), m.group(3))
-    return out
-
-
 def test_devarith_flags_are_the_product_hipflags():
-    product = _assignments(os.path.join(ROOT, "syzygy_amd", "csrc", "Makefile"))
-    tests = _assignments(os.path.join(HERE, "Makefile"))
+    product = native.assignments(os.path.join(ROOT, "syzygy_amd", "csrc", "Makefile"))
+    tests = native.assignments(os.path.join(HERE, "Makefile"))
     op, hipflags = product["HIPFLAGS"]
     assert op == "?="
     want = hipflags.replace("$(ARCH)", product["ARCH"][1]).split()

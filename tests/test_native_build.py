@@ -9,7 +9,6 @@ import time
 import pytest
 
 from tests import native
-from tests.test_device_arith_build import _assignments
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -78,7 +77,7 @@ def test_the_tests_ask_for_exactly_the_targets_of_the_makefile():
         if path != os.path.abspath(__file__):  # the toy's call names a directory too; every other call is a literal target
             assert len(calls) == text.count("native.build("), path
         asked |= set(calls)
-    variables = _assignments(os.path.join(HERE, "Makefile"))
+    variables = native.assignments(os.path.join(HERE, "Makefile"))
     defined = variables["TARGETS"][1]
     while "$(" in defined:
         defined = re.sub(r"\$\((\w+)\)", lambda m: variables[m.group(1)][1], defined)
