@@ -70,6 +70,9 @@ def main(argv=None):
                          "(default), reference (the reference sampler's 1.0) or a number")
     ap.add_argument("--anisotropy", default=None, metavar="A",
                     help="with --mipmaps: the sampler's maxAnisotropy, 1 to 16 (szg/anisotropy.h); default off (1, the reference's)")
+    ap.add_argument("--multiscatter", nargs="?", const="add", default=None, choices=("add", "only"), metavar="add|only",
+                    help="multiple scattering in the sky-view LUT (szg/multiscatter_sky.h): the higher orders added to the sky, or "
+                         "alone; the frame then records the multi-scattering LUT as well. Default off (the reference's single scattering)")
     ap.add_argument("--ui-layer", action="store_true",
                     help="draw an editor-like UI frame over the scene (szg/ui_layer.h) and present the UI output texture")
     ap.add_argument("--texture-viewer", nargs="?", const="color", default=None, choices=["color", "normal", "orm", "gbuffer-normal"],
@@ -150,6 +153,8 @@ def main(argv=None):
     target = ui_layer.sceneTexture() if ui_layer else pl.SceneTexture(W, H)
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=len(spots), max_shadow_maps=2 + len(spots), shadow_map_dim=args.shadow_map)
     sky = pl.SkyViewComputePipeline.create()
+    if args.multiscatter:  # recordDrawCommands then records transmittance, multi-scatter, sky-view and composite
+        sky.setMultiScattering({"add": abi.SZG_MULTISCATTER_ADD, "only": abi.SZG_MULTISCATTER_ONLY}[args.multiscatter])
     rect = ui_layer.sceneViewport().renderedSubregion if ui_layer else pl.rect(W, H)  # editor.cpp:720-735: the viewport's subregion
     RW, RH = rect.width, rect.height
     debug_lines = pl.DebugLines()  # Renderer::m_debugLines, DEBUGLINES_CAPACITY vertices (renderer.hpp:103)

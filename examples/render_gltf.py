@@ -67,6 +67,9 @@ def main(argv=None):
                          "(default), reference (the reference sampler's 1.0) or a number")
     ap.add_argument("--anisotropy", default=None, metavar="A",
                     help="with --mipmaps: the sampler's maxAnisotropy, 1 to 16 (szg/anisotropy.h); default off (1, the reference's)")
+    ap.add_argument("--multiscatter", nargs="?", const="add", default=None, choices=("add", "only"), metavar="add|only",
+                    help="multiple scattering in the sky-view LUT (szg/multiscatter_sky.h): the higher orders added to the sky, or "
+                         "alone; the frame then records the multi-scattering LUT as well. Default off (the reference's single scattering)")
     ap.add_argument("--jpeg", nargs="?", const="host", default=None, choices=("host", "device"), metavar="host|device",
                     help="decode JPEG material maps (szg/jpeg.h; default: PNG only, as before): on the host, or the entropy decode on "
                          "the host and IDCT, upsampling and colour conversion on the GPU")
@@ -148,6 +151,8 @@ def main(argv=None):
     target = pl.SceneTexture(W, H)
     deferred = pl.DeferredShadingPipeline((W, H), max_spot_lights=1, max_shadow_maps=3, shadow_map_dim=2048)
     sky = pl.SkyViewComputePipeline.create()
+    if args.multiscatter:  # recordDrawCommands then records transmittance, multi-scatter, sky-view and composite
+        sky.setMultiScattering({"add": abi.SZG_MULTISCATTER_ADD, "only": abi.SZG_MULTISCATTER_ONLY}[args.multiscatter])
     rect = pl.rect(W, H)
     if pipeline == "compute-collection":  # renderer.cpp:431-438: the collection only
         collection = pl.ComputeCollectionPipeline()

@@ -440,9 +440,11 @@ int szg_skyview_record_composite_fast(szg_skyview_t* p, void* stream, const szg_
  * (8 x 8 stratified), each a 20-step march accumulating the 2nd-order in-scattered luminance L2 and the transfer
  * factor f_ms with the reference's own extinction / sun-transmittance functions (common.glinl:145-216) and the
  * ground term of camera.comp:203-227 (albedo 0.4 / pi); texel = mean(L2) / (1 - mean(f_ms)). One 64-lane wavefront
- * per texel, lane = direction, butterfly reduction across the wave. Opt-in and NOT consumed by any parity pass:
- * adding it to the scattering integral would change results. Validated against the scalar oracle
- * (same reduction tree) and by energy sanity (0 <= f_ms < 1). */
+ * per texel, lane = direction, butterfly reduction across the wave. Opt-in. Consumed by the sky-view and aerial LUT
+ * passes of a pipeline whose multi-scattering mode is set (szg/multiscatter_sky.h: szg_skyview_set_multiscatter), and by
+ * nothing while the mode is SZG_MULTISCATTER_OFF, the default: adding it to the scattering integral changes results
+ * (SURVEY a17), so the parity frame stays single scattering. Validated against the scalar oracle (same reduction tree)
+ * and by energy sanity (0 <= f_ms < 1). */
 #define SZG_MULTISCATTER_DIM 32u
 int szg_skyview_record_multiscatter_lut(szg_skyview_t* p, void* stream, uint32_t atmosphere_index,
                                         const szg_atmosphere_packed* d_atmospheres);

@@ -40,6 +40,7 @@
 #include "szg/compute_collection.h"
 #include "szg/debuglines.h"
 #include "szg/mipmaps.h"
+#include "szg/multiscatter_sky.h"
 #include "szg/present.h"
 #include "szg/raster.h"
 #include "szg/texture_display.h"
@@ -391,6 +392,18 @@ struct SkyViewComputePipeline
     [[nodiscard]] auto lastStatus() const -> int { return m_lastStatus; } // status of the last record call (SZG_OK or negative)
     void setLUTReuse(bool enable) { (void)szg_skyview_set_lut_reuse(m_handle, enable ? 1 : 0); }
     void invalidateLUTs(uint32_t which = SZG_LUT_TRANSMITTANCE | SZG_LUT_SKYVIEW) { (void)szg_skyview_invalidate_luts(m_handle, which); }
+    // szg/multiscatter_sky.h: SZG_MULTISCATTER_OFF (the reference's single scattering, the default), _ADD or _ONLY. With a mode
+    // set recordDrawCommands records the multi-scattering LUT between the transmittance and the sky-view LUT.
+    auto setMultiScattering(uint32_t mode) -> int
+    {
+        return detail::note(szg_skyview_set_multiscatter(m_handle, mode), "szg_skyview_set_multiscatter", m_lastStatus);
+    }
+    [[nodiscard]] auto multiScattering() const -> uint32_t
+    {
+        uint32_t mode = SZG_MULTISCATTER_OFF;
+        (void)szg_skyview_get_multiscatter(m_handle, &mode);
+        return mode;
+    }
     // Row-tiled multi-GPU frame: transmittance LUT, this rank's slice of the sky-view LUT, the all-gather of the slices on
     // `lutStream` (ordered behind `cmd` by an event), then the composite on `cmd` once the LUT is complete.
     void recordDrawCommandsTiled(hipStream_t cmd, hipStream_t lutStream, hipEvent_t scratchEvent, szg_rowtile_comm_t* comm,

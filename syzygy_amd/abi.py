@@ -722,6 +722,16 @@ LIGHT_TILE_FUNCTIONS = {
 }
 
 
+# include/szg/multiscatter_sky.h
+SZG_MULTISCATTER_OFF = 0
+SZG_MULTISCATTER_ADD = 1
+SZG_MULTISCATTER_ONLY = 2
+MULTISCATTER_SKY_FUNCTIONS = {
+    "szg_skyview_set_multiscatter": (C.c_int, [VP, U32]),
+    "szg_skyview_get_multiscatter": (C.c_int, [VP, P(U32)]),
+}
+
+
 # What syzygy_amd._lib.lib() binds, in this order: (header, table, notice). A header named here was added without moving the
 # ABI version, so a build of the same version may predate it: lib() then says which header is missing (for the first five,
 # which the version itself covers, a missing export stays an AttributeError). `notice` None: the table must always bind;
@@ -740,6 +750,7 @@ BINDINGS = [
     ("texture_display.h", TEXTURE_DISPLAY_FUNCTIONS, "the texture viewer is unavailable with it"),
     ("light_tiles.h", LIGHT_TILE_FUNCTIONS, "the light tile masks cannot be read back with it"),
     ("anisotropy.h", ANISOTROPY_FUNCTIONS, "anisotropic filtering is unavailable with it"),
+    ("multiscatter_sky.h", MULTISCATTER_SKY_FUNCTIONS, "multiple scattering in the sky-view and aerial LUTs is unavailable with it"),
 ]
 
 

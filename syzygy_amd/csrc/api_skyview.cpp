@@ -4,6 +4,7 @@
 
 #include "api_common.hpp"
 #include "lut_state.hpp"
+#include "szg/multiscatter_sky.h"
 
 using namespace szg;
 
@@ -13,6 +14,7 @@ struct szg_skyview
     szg_skyview_desc desc{};
     DeviceBuffer<float> d_transmittance, d_skyview, d_multiscatter, d_aerialLuminance, d_aerialTransmittance;
     float aerialMaxDistance = 0.0f; // 0 = never recorded
+    uint32_t multiscatter = SZG_MULTISCATTER_OFF; // szg/multiscatter_sky.h: the mode of the sky-view and aerial LUT passes
     // mutable: the accessors that hand texels out take the ABI's const handle, and handing out is an event
     mutable LutState luts;
     DeviceBuffer<unsigned> d_slutStatusAll; // szg::SLUT_STATUS_RANKS dwords: the ranks' slice status words (szg_skyview_allgather_lut_rows)
@@ -33,6 +35,20 @@ static hipError_t ensure_tlut_status(szg_skyview* p, hipStream_t s)
         return e == hipSuccess;
     });
     return e;
+}
+
+// A LUT pass with a mode set reads the multi-scattering LUT: somebody must have written it (szg/multiscatter_sky.h "WHERE").
+static bool multiscatter_ready(const szg_skyview* p, const char* call)
+{
+    if (p->multiscatter != SZG_MULTISCATTER_OFF && !p->luts.multiscatterPresent)
+    {
+        fail(SZG_ERR_INVALID_ARGUMENT,
+             "%s: multi-scattering mode %u is set but this pipeline holds no multi-scattering LUT: record one with "
+             "szg_skyview_record_multiscatter_lut (or upload one through szg_skyview_multiscatter_lut) first",
+             call, p->multiscatter);
+        return false;
+    }
+    return true;
 }
 
 static hipError_t ensure_slut_status(szg_skyview* p, hipStream_t s)
@@ -105,6 +121,30 @@ int szg_skyview_set_lut_reuse(szg_skyview_t* p, int enable)
     p->lutReuse = enable != 0;
     // whatever was computed while reuse was off has no key on the device: the first frame after a switch recomputes
     p->luts.reuse_switched();
+    return SZG_OK;
+}
+
+int szg_skyview_set_multiscatter(szg_skyview_t* p, uint32_t mode)
+{
+    if (p == nullptr || mode > SZG_MULTISCATTER_ONLY)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_skyview_set_multiscatter: NULL pipeline or unknown mode %u", mode);
+    }
+    if (mode != p->multiscatter)
+    {
+        p->multiscatter = mode;
+        p->luts.multiscatter_mode_changed();
+    }
+    return SZG_OK;
+}
+
+int szg_skyview_get_multiscatter(const szg_skyview_t* p, uint32_t* mode)
+{
+    if (p == nullptr || mode == nullptr)
+    {
+        return fail(SZG_ERR_INVALID_ARGUMENT, "szg_skyview_get_multiscatter: NULL argument");
+    }
+    *mode = p->multiscatter;
     return SZG_OK;
 }
 
@@ -193,6 +233,10 @@ int szg_skyview_record_skyview_lut_rows(szg_skyview_t* p, void* stream, uint32_t
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_skyview_record_skyview_lut_rows: rows [%u, %u) outside the %u-row LUT", row_begin,
                     row_end, p->desc.skyview_height);
     }
+    if (!multiscatter_ready(p, "szg_skyview_record_skyview_lut_rows"))
+    {
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
     DeviceGuard const guard(p->device);
     hipStream_t const s = static_cast<hipStream_t>(stream);
     bool const whole = LutState::whole(row_begin, row_end, p->desc.skyview_height);
@@ -206,9 +250,19 @@ int szg_skyview_record_skyview_lut_rows(szg_skyview_t* p, void* stream, uint32_t
     }
     SZG_HIP(szg::launch_frame_prep(s, d_atmospheres, atmosphere_index, p->desc.transmittance_width, p->desc.transmittance_height,
                                    p->d_framePrep));
-    SZG_HIP(szg::launch_skyview(s, d_atmospheres, atmosphere_index, d_cameras, view_camera_index, p->d_transmittance,
-                                p->desc.transmittance_width, p->desc.transmittance_height, p->d_skyview, p->desc.skyview_width,
-                                p->desc.skyview_height, row_begin, row_end, dirty, p->d_framePrep));
+    if (p->multiscatter == SZG_MULTISCATTER_OFF)
+    {
+        SZG_HIP(szg::launch_skyview(s, d_atmospheres, atmosphere_index, d_cameras, view_camera_index, p->d_transmittance,
+                                    p->desc.transmittance_width, p->desc.transmittance_height, p->d_skyview, p->desc.skyview_width,
+                                    p->desc.skyview_height, row_begin, row_end, dirty, p->d_framePrep));
+    }
+    else
+    {
+        SZG_HIP(szg::launch_skyview_ms(s, p->multiscatter, d_atmospheres, atmosphere_index, d_cameras, view_camera_index,
+                                       p->d_transmittance, p->desc.transmittance_width, p->desc.transmittance_height,
+                                       p->d_multiscatter, p->d_skyview, p->desc.skyview_width, p->desc.skyview_height, row_begin,
+                                       row_end, dirty, p->d_framePrep));
+    }
     // (a slice is never launched behind a reuse key: launch_skyview cleared the status dword, the slice's waves set it)
     p->luts.skyview_rows_recorded(row_begin, row_end, p->desc.skyview_height);
     return SZG_OK;
@@ -379,6 +433,7 @@ int szg_skyview_record_multiscatter_lut(szg_skyview_t* p, void* stream, uint32_t
     SZG_HIP(szg::launch_multiscatter(static_cast<hipStream_t>(stream), d_atmospheres, atmosphere_index, p->d_transmittance,
                                      p->desc.transmittance_width, p->desc.transmittance_height, p->d_multiscatter,
                                      SZG_MULTISCATTER_DIM));
+    p->luts.multiscatter_recorded(p->multiscatter != SZG_MULTISCATTER_OFF);
     return SZG_OK;
 }
 
@@ -389,6 +444,7 @@ int szg_skyview_multiscatter_lut(const szg_skyview_t* p, szg_image* out)
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_skyview_multiscatter_lut: NULL argument");
     }
     *out = make_image(p->d_multiscatter, SZG_MULTISCATTER_DIM, SZG_MULTISCATTER_DIM, SZG_FORMAT_RGBA32_SFLOAT);
+    p->luts.multiscatter_exposed(p->multiscatter != SZG_MULTISCATTER_OFF); // the caller may write the texels through this view
     return SZG_OK;
 }
 
@@ -404,12 +460,26 @@ int szg_skyview_record_aerial_lut(szg_skyview_t* p, void* stream, uint32_t atmos
     {
         return fail(SZG_ERR_INVALID_ARGUMENT, "szg_skyview_record_aerial_lut: max_distance_mm must be in (0, 1e6)");
     }
+    if (!multiscatter_ready(p, "szg_skyview_record_aerial_lut"))
+    {
+        return SZG_ERR_INVALID_ARGUMENT;
+    }
     DeviceGuard const guard(p->device);
     SZG_HIP(ensure_tlut_status(p, static_cast<hipStream_t>(stream)));
-    SZG_HIP(szg::launch_aerial_lut(static_cast<hipStream_t>(stream), d_atmospheres, atmosphere_index, d_cameras, view_camera_index,
-                                   p->d_transmittance, p->desc.transmittance_width, p->desc.transmittance_height,
-                                   p->d_aerialLuminance, p->d_aerialTransmittance, SZG_AERIAL_W, SZG_AERIAL_H, SZG_AERIAL_D,
-                                   max_distance_mm));
+    if (p->multiscatter == SZG_MULTISCATTER_OFF)
+    {
+        SZG_HIP(szg::launch_aerial_lut(static_cast<hipStream_t>(stream), d_atmospheres, atmosphere_index, d_cameras, view_camera_index,
+                                       p->d_transmittance, p->desc.transmittance_width, p->desc.transmittance_height,
+                                       p->d_aerialLuminance, p->d_aerialTransmittance, SZG_AERIAL_W, SZG_AERIAL_H, SZG_AERIAL_D,
+                                       max_distance_mm));
+    }
+    else
+    {
+        SZG_HIP(szg::launch_aerial_lut_ms(static_cast<hipStream_t>(stream), p->multiscatter, d_atmospheres, atmosphere_index, d_cameras,
+                                          view_camera_index, p->d_transmittance, p->desc.transmittance_width,
+                                          p->desc.transmittance_height, p->d_multiscatter, p->d_aerialLuminance,
+                                          p->d_aerialTransmittance, SZG_AERIAL_W, SZG_AERIAL_H, SZG_AERIAL_D, max_distance_mm));
+    }
     p->aerialMaxDistance = max_distance_mm;
     return SZG_OK;
 }
@@ -433,6 +503,11 @@ int szg_skyview_record_draw_commands(szg_skyview_t* p, void* stream, const szg_s
 {
     // skyview.cpp:795-845, :847-893, :895-910: three dispatches in this order, every frame.
     SZG_TRY_RC(szg_skyview_record_transmittance(p, stream, atmosphere_index, d_atmospheres));
+    if (p != nullptr && p->multiscatter != SZG_MULTISCATTER_OFF)
+    {
+        // szg/multiscatter_sky.h: the LUT the sky-view pass is about to read, from this frame's transmittance LUT
+        SZG_TRY_RC(szg_skyview_record_multiscatter_lut(p, stream, atmosphere_index, d_atmospheres));
+    }
     SZG_TRY_RC(szg_skyview_record_skyview_lut(p, stream, atmosphere_index, d_atmospheres, view_camera_index, d_cameras));
     return szg_skyview_record_composite(p, stream, scene_texture, draw_rect, tile, gbuffer, shadow_maps, atmosphere_index,
                                         d_atmospheres, view_camera_index, d_cameras, sun_light_index, d_lights);

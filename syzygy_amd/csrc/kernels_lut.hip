@@ -10,6 +10,7 @@
 #include "szg_atmosphere.hpp"
 #include "szg_launch.hpp"
 #include "szg_lean.hpp"
+#include "szg_lut_rays.hpp"
 #include "szg_march.hpp"
 #include "szg_vec.hpp"
 
@@ -268,46 +269,8 @@ __global__ __launch_bounds__(256, 4) void k_skyview(const szg_atmosphere_packed*
     Atm const a = load_atm(*prep); // (k_frame_prep: load_atm(atmospheres + atmosphereIndex), once per frame instead of once per wave)
     TLut const L = make_tlut(tlut, tW, tH, *prep);
     const szg_camera_packed* cam = cameras + cameraIndex;
-    float const PI = 3.141592653589793f;
-
-    // skyview_LUT.comp:100-101
-    float const u = ((float)x + 0.5f) / (float)W;
-    float const v = ((float)y + 0.5f) / (float)H;
-
-    // skyview_LUT.comp:110-112
-    V3 origin = mk3(cam->position[0], cam->position[1], cam->position[2]) / 1000000.0f;
-    origin.y *= -1.0f;
-    origin.y += a.planetRadius;
-
-    // uv_to_azimuthElevation, skyview_LUT.comp:51-89
-    float const radius = length(origin);
-    float const sinHorizonZenith = a.planetRadius / radius;
-    float const horizonZenith = PI - szg_asinf(sinHorizonZenith);
-    float const cosineViewLightProjected = (u - 0.5f) * 2.0f;
-    V2 const lightDirectionProjected = normalize(V2{-a.incidentDirectionSun.x, -a.incidentDirectionSun.z});
-    float azimuthSun = szg_asinf(lightDirectionProjected.x);
-    if (lightDirectionProjected.y < 0.0f)
-    {
-        azimuthSun = PI - azimuthSun;
-    }
-    float const azimuth = szg_acosf(clampf(cosineViewLightProjected, -1.0f, 1.0f)) + azimuthSun;
-    float viewZenith;
-    float const unnormalized_v = 2.0f * v - 1.0f;
-    if (v < 0.5f)
-    {
-        float const angleFraction = 1.0f - unnormalized_v * unnormalized_v;
-        viewZenith = angleFraction * horizonZenith;
-    }
-    else
-    {
-        float const angleFraction = unnormalized_v * unnormalized_v;
-        viewZenith = (PI - horizonZenith) * angleFraction + horizonZenith;
-    }
-    float const elevation = -(viewZenith - PI / 2.0f);
-
-    // skyview_LUT.comp:118-119
-    float const ce = szg_cosf(elevation);
-    V3 const direction = normalize(mk3(szg_sinf(azimuth) * ce, szg_sinf(elevation), szg_cosf(azimuth) * ce));
+    V3 origin, direction;
+    skyviewTexelRay(a, cam, x, y, W, H, origin, direction);
 
     float const distance = raycastAtmosphere(a, origin, direction);
     V3 const luminance = scatteringIntegral(L, a, origin, direction, distance);
@@ -378,16 +341,8 @@ __global__ __launch_bounds__(256) void k_aerial_lut(const szg_atmosphere_packed*
     TLut const L = make_tlut(tlut, tW, tH);
     const szg_camera_packed* cam = cameras + cameraIndex;
 
-    // camera.comp:320-328 with the froxel centre as the (continuous) pixel coordinate
-    V3 position = mk3(cam->position[0], cam->position[1], cam->position[2]) / 1000000.0f;
-    position.y *= -1.0f;
-    position.y += a.planetRadius;
-    float const clipx = (((float)i + 0.5f) / (float)W - 0.5f) * 2.0f;
-    float const clipy = (((float)j + 0.5f) / (float)H - 0.5f) * 2.0f;
-    V4 const dvs = mul(load_m4(cam->inverseProjection), clipx, clipy, 1.0f, 1.0f);
-    V4 const rot = mul(load_m4(cam->rotation), dvs.x, dvs.y, dvs.z, dvs.w);
-    V3 direction = normalize(mk3(rot.x, rot.y, rot.z));
-    direction.y *= -1.0f;
+    V3 position, direction;
+    aerialFroxelRay(a, cam, i, j, W, H, position, direction);
 
     float const d = (((float)k + 0.5f) / (float)D) * maxDistance;
     V3 const lum = scatteringIntegral(L, a, position, direction, d);

@@ -49,6 +49,27 @@ struct LutState
         sliceRowBegin = rowBegin;
         sliceRowEnd = rowEnd;
     }
+    // Multi-scattering LUT (szg/multiscatter_sky.h). `multiscatterPresent`: the pipeline holds texels somebody wrote (the LUT
+    // pass, or a caller through the accessor); a record call with a mode set is refused without them.
+    bool multiscatterPresent = false;
+    // the mode decides what every sky-view texel is: texels computed under another mode are stale
+    void multiscatter_mode_changed() { forceSkyview = true; }
+    // recorded by the library: the texels are a function of the atmosphere block and the transmittance LUT, both of which the
+    // reuse key of the sky-view LUT covers (the block itself, and the transmittance LUT's generation): nothing to force
+    // ... unless the texels it replaces were handed out before: those were a function of nothing the key knows
+    void multiscatter_recorded(bool modeSet)
+    {
+        forceSkyview = forceSkyview || (modeSet && multiscatterHandedOut);
+        multiscatterPresent = true;
+        multiscatterHandedOut = false;
+    }
+    // handed out through a view the caller may write through; the sky-view LUT reads the texels only while a mode is set
+    bool multiscatterHandedOut = false;
+    void multiscatter_exposed(bool modeSet)
+    {
+        multiscatterPresent = multiscatterHandedOut = true;
+        forceSkyview = forceSkyview || modeSet;
+    }
     // all-gather of row slices: may rank `rank` of `nranks` stage the status dword as the status of its slice?
     bool slice_status_known(uint32_t rank, uint32_t nranks, uint32_t height) const
     {

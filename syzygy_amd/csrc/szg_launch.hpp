@@ -113,6 +113,17 @@ hipError_t launch_aerial_lut(hipStream_t s, const szg_atmosphere_packed* d_atm, 
                              unsigned W, unsigned H, unsigned D, float maxDistance);
 hipError_t launch_multiscatter(hipStream_t s, const szg_atmosphere_packed* d_atm, unsigned atmIndex, const float* tlut, unsigned tW,
                                unsigned tH, float* out, unsigned dim);
+// launch_skyview / launch_aerial_lut with the multi-scattering term of include/szg/multiscatter_sky.h in the march
+// (kernels_lut_ms.hip). `mode`: SZG_MULTISCATTER_ADD or _ONLY (anything else: hipErrorInvalidValue); `psi`: the
+// SZG_MULTISCATTER_DIM^2 RGBA32F texels of the multi-scattering LUT.
+hipError_t launch_skyview_ms(hipStream_t s, unsigned mode, const szg_atmosphere_packed* d_atm, unsigned atmIndex,
+                             const szg_camera_packed* d_cam, unsigned camIndex, const float* tlut, unsigned tW, unsigned tH,
+                             const float* psi, float* lut, unsigned W, unsigned H, unsigned rowBegin, unsigned rowEnd,
+                             const unsigned* d_dirty, const void* d_prep);
+hipError_t launch_aerial_lut_ms(hipStream_t s, unsigned mode, const szg_atmosphere_packed* d_atm, unsigned atmIndex,
+                                const szg_camera_packed* d_cam, unsigned camIndex, const float* tlut, unsigned tW, unsigned tH,
+                                const float* psi, float* luminance, float* transmittance, unsigned W, unsigned H, unsigned D,
+                                float maxDistance);
 
 // ---- deferred lights pass (kernels_lights.hip) ----
 hipError_t launch_light_prep(hipStream_t s, const szg_directional_light_packed* d_dir, unsigned dirCount, unsigned dirSkip,

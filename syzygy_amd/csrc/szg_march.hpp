@@ -49,9 +49,16 @@ struct MarchSetup
 };
 
 // INNER: every radius of the march lies below Atm::innerCeil2 (wave-uniform, decided per ray in scatteringIntegral)
-template <bool LEAN, bool INNER = false> SZG_DEV V3 marchLoop(const TLut& L, const Atm& a, const MarchSetup& m)
+// MS: the multi-scattering mode of include/szg/multiscatter_sky.h (0 = off: `psi` is not read and the function is what it was
+// before that header; 1 = the higher orders added to the result; 2 = the higher orders alone). `psi`: the SZG_MULTISCATTER_DIM^2
+// RGBA32F texels of the multi-scattering LUT, in global memory or in LDS. The term reads values the three bodies form alike
+// (s_musun, altitude, the two scattering coefficients, integral, T_begin), so it does not depend on the body either.
+template <bool LEAN, bool INNER = false, int MS = 0>
+SZG_DEV V3 marchLoop(const TLut& L, const Atm& a, const MarchSetup& m, const float4* psi = nullptr)
 {
     V3 luminance = splat(0.0f);
+    V3 ms = splat(0.0f);
+    float const shell = a.atmosphereRadius - a.planetRadius;
     // `end` of step i and `begin` of step i+1 are the same expression (common.glinl:386-387),
     // so its length and radius part are carried from one iteration to the next.
     V3 begin = fnma(0.0f * m.dS, m.scatteringDir, m.origin);
@@ -152,15 +159,25 @@ template <bool LEAN, bool INNER = false> SZG_DEV V3 marchLoop(const TLut& L, con
                                                      divN0(oneMinusT.z, ex.extinction.z)}
                                                 : oneMinusT / ex.extinction;
         luminance = fma3(phaseTimesScattering * T_sun * integral, T_begin, luminance);
+        if (MS != 0)
+        {
+            // szg/multiscatter_sky.h "THE RULE": the sample's sun cosine with `begin`'s altitude, the pairing of the term above
+            float const su = clampf(0.5f + 0.5f * s_musun, 0.0f, 1.0f);
+            float const sv = clampf(altitude / shell, 0.0f, 1.0f);
+            V3 const Psi = bilinear_rgb(psi, (int)SZG_MULTISCATTER_DIM, (int)SZG_MULTISCATTER_DIM, (float)SZG_MULTISCATTER_DIM,
+                                        (float)SZG_MULTISCATTER_DIM, su, sv);
+            ms = fma3(((ex.scatteringRayleigh + ex.scatteringMie) * Psi) * integral, T_begin, ms);
+        }
 
         begin = end;
         lenBegin = lenEnd;
         pBegin = pEnd;
     }
-    return luminance;
+    return MS == 0 ? luminance : (MS == 1 ? luminance + ms : ms);
 }
 
-SZG_DEV V3 scatteringIntegral(const TLut& L, const Atm& a, V3 origin, V3 direction, float sampleDistance)
+template <int MS = 0>
+SZG_DEV V3 scatteringIntegral(const TLut& L, const Atm& a, V3 origin, V3 direction, float sampleDistance, const float4* psi = nullptr)
 {
     MarchSetup m;
     m.origin = origin;
@@ -238,11 +255,11 @@ SZG_DEV V3 scatteringIntegral(const TLut& L, const Atm& a, V3 origin, V3 directi
         // the taps are quotients bounded by Cauchy-Schwarz up to rounding (|mu| <= 1 + 2^-20 is all INNER asks for)
         if (waveAll(fmaxf(m.r2, L2) <= a.innerCeil2))
         {
-            return marchLoop<true, true>(L, a, m);
+            return marchLoop<true, true, MS>(L, a, m, psi);
         }
-        return marchLoop<true, false>(L, a, m);
+        return marchLoop<true, false, MS>(L, a, m, psi);
     }
-    return marchLoop<false>(L, a, m);
+    return marchLoop<false, false, MS>(L, a, m, psi);
 }
 
 } // namespace szg

@@ -863,6 +863,16 @@ class SkyViewComputePipeline:
     def multiScatterLUT(self):
         return self._lut(lib().szg_skyview_multiscatter_lut)
 
+    def setMultiScattering(self, mode):
+        """Extension (szg/multiscatter_sky.h): abi.SZG_MULTISCATTER_OFF (default: the reference's single scattering), _ADD
+        (the sky-view and aerial LUT passes add the higher orders from the multi-scattering LUT) or _ONLY (those alone)."""
+        check(lib().szg_skyview_set_multiscatter(self._h, int(mode)))
+
+    def multiScattering(self):
+        mode = C.c_uint32()
+        check(lib().szg_skyview_get_multiscatter(self._h, C.byref(mode)))
+        return int(mode.value)
+
     def recordAerialLUT(self, cmd, atmosphereIndex, atmospheres, viewCameraIndex, cameras, maxDistanceMm):
         """Extension (no reference counterpart, abi.h): aerial-perspective froxel LUT, exact texel values."""
         check(lib().szg_skyview_record_aerial_lut(self._h, _stream_handle(cmd), int(atmosphereIndex),
