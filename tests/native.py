@@ -17,9 +17,8 @@ MAKE_TIMEOUT = 130
 
 
 def sources(directory=TESTS):
-    """Every source file of the native test programs."""
-    return sorted(f for sub in ("cpp", "jpeg", "mipsample") for ext in ("*.cpp", "*.hip", "*.hpp", "*.h")
-                  for f in glob.glob(os.path.join(directory, sub, ext)))
+    """Every source file of the native test programs: the C++ and HIP files of every directory directly under tests/."""
+    return sorted(f for ext in ("*.cpp", "*.hip", "*.hpp", "*.h") for f in glob.glob(os.path.join(directory, "*", ext)))
 
 
 def wanted_stamp(directory, hashed):
@@ -37,7 +36,8 @@ def build(target, directory=TESTS, hashed=None):
     untracked, where file times say nothing, so a target is fresh only if it exists and the stamp written after its last build
     equals the hash of the current sources; then nothing runs. Otherwise `make -B <target>`, whatever file times say. The
     hash is deliberately the same for every target: any change of the product or of a test program rebuilds each target the
-    next time it is asked for. The mirror programs link against libszg_hip.so, which has to be built first."""
+    next time it is asked for. The mirror programs link against libszg_hip.so, which has to be built first. The tests call
+    build("<dir>/<target>") and nothing else; `directory` and `hashed` are for the toy tree of tests/test_native_build.py."""
     artefact = os.path.join(directory, target)
     stamp = artefact + ".build_stamp"
     want = wanted_stamp(directory, sources(directory) if hashed is None else hashed)
@@ -72,3 +72,26 @@ def commands(target, directory=TESTS):
     """The command lines `make` would run for `target` (make -n -B: nothing is built)."""
     return subprocess.run(["make", "-n", "-B", "-C", directory, "--no-print-directory", target], check=True, capture_output=True,
                           text=True, timeout=MAKE_TIMEOUT).stdout.splitlines()
+
+
+def resource_remarks(target, fields):
+    """kernel name -> {field: figure} of what the compiler reports for the kernels of `make <target>` in syzygy_amd/csrc
+    (-Rpass-analysis=kernel-resource-usage; the library's flags and per-unit scheduler options). `fields` maps a field to the
+    pattern of its figure; only the remark lines are read."""
+    csrc = os.path.join(os.path.dirname(TESTS), "syzygy_amd", "csrc")
+    done = subprocess.run(["make", "-C", csrc, target], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                          timeout=MAKE_TIMEOUT)
+    assert done.returncode == 0, done.stdout[-4000:]
+    kernels, current = {}, None
+    for line in done.stdout.splitlines():
+        if "remark:" not in line:
+            continue
+        name = re.search(r"Function Name: (\S+)", line)
+        if name:
+            current = kernels.setdefault(name.group(1), {})
+            continue
+        for field, pattern in fields.items():
+            m = re.search(pattern, line)
+            if m and current is not None:
+                current[field] = int(m.group(1))
+    return kernels

@@ -268,16 +268,6 @@ def test_set_sampler_anisotropy_refuses(name):
     assert b"szg_deferred_set_sampler_anisotropy" in message and text in message, message
 
 
-def test_the_test_kernel_is_compiled_as_the_product_is():
-    """tests/anisosample/Makefile builds its kernel with the DEVICE_FLAGS of tests/Makefile, which tests/test_device_arith_build.py
-    holds equal to the product's HIPFLAGS."""
-    def flags(path):
-        return re.search(r"^DEVICE_FLAGS = (.*)$", open(os.path.join(ROOT, "tests", path)).read(), flags=re.M).group(1)
-
-    assert flags(os.path.join("anisosample", "Makefile")) == flags("Makefile")
-    assert "-ffp-contract=off" in flags("Makefile")
-
-
 def test_the_examples_anisotropy_switch():
     from syzygy_amd import pipelines
 

@@ -1,6 +1,6 @@
 """The test libraries around the product's device code - tests/cpp/libszg_devarith.so (tests/test_gpu_device_arith.py),
-tests/cpp/libszg_marchrays.so (tests/test_gpu_march_rays.py), tests/mipsample/libszg_mipsample.so (tests/test_gpu_mipmaps.py):
-they cross-compile for gfx950 without a GPU, and they are compiled with the product's HIPFLAGS (a sweep of code built with
+tests/cpp/libszg_marchrays.so (tests/test_gpu_march_rays.py), tests/mipsample/libszg_mipsample.so (tests/test_gpu_mipmaps.py),
+tests/anisosample/libszg_anisosample.so (tests/test_gpu_anisotropy.py): they cross-compile for gfx950 without a GPU, and they are compiled with the product's HIPFLAGS (a sweep of code built with
 other flags says nothing about the kernels). tests/cpp/libszg_marchrays_literal.so is the march harness once more with
 -DSZG_LITERAL, for the literal pair (tests/literal_pair.py): the plain rule's command line plus that one define."""
 import os
@@ -10,7 +10,7 @@ from tests import native
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-LIBRARIES = ("cpp/libszg_devarith.so", "cpp/libszg_marchrays.so", "mipsample/libszg_mipsample.so")
+LIBRARIES = ("cpp/libszg_devarith.so", "cpp/libszg_marchrays.so", "mipsample/libszg_mipsample.so", "anisosample/libszg_anisosample.so")
 LITERAL_LIBRARIES = {"cpp/libszg_marchrays_literal.so": "cpp/libszg_marchrays.so"}  # literal target -> the plain one of the same source
 
 
@@ -24,8 +24,8 @@ def test_devarith_flags_are_the_product_hipflags():
     assert tests["DEVICE_FLAGS"][1].split() == want
     assert tests["DEVICE_LIBS"][1].split() == list(LIBRARIES) + list(LITERAL_LIBRARIES)
     rule = open(os.path.join(HERE, "Makefile")).read()
-    # the three are built by the one pattern rule, which adds no flag of its own
-    assert not re.search(r"^[^#\n]*libszg_(devarith|marchrays|mipsample)\.so.*:", rule, re.M)
+    # the four are built by the one pattern rule, which adds no flag of its own
+    assert not re.search(r"^[^#\n]*libszg_(devarith|marchrays|mipsample|anisosample)\.so.*:", rule, re.M)
     recipe = re.search(r"^libszg_%\.so:.*\n\t(.*)$", rule, re.M).group(1)
     assert "$(DEVICE_FLAGS)" in recipe and not re.search(r"\s-(O\d|f|m|std|-offload)", recipe.replace("$(DEVICE_FLAGS)", ""))
     for target in LIBRARIES:  # and what make then runs: the compiler, the product's flags, and no such flag after them

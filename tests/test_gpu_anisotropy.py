@@ -1,8 +1,7 @@
 """include/szg/anisotropy.h on the GPU: the device sampler of syzygy_amd/csrc/szg_texture.hpp in isolation, called by the
-test-only kernel of tests/anisosample (built by its own make rule with the product's HIPFLAGS), bit for bit against
+test-only kernel of tests/anisosample (built by the DEVICE_LIBS rule of tests/Makefile with the product's HIPFLAGS), bit for bit against
 tests/aniso_model.py; at max_anisotropy 1 also against the trilinear test kernel of tests/mipsample."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -11,12 +10,10 @@ from syzygy_amd import abi
 from tests import aniso_model as am
 from tests import mipmap_model as mm
 from tests import native
-from tests.native import build as build_native  # the kernel's library has its own Makefile, not a target of tests/Makefile
 from tests.test_gpu_mipmaps import N, _samples
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "anisosample")
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +27,7 @@ def torch():
 
 @pytest.fixture(scope="module")
 def anisosample():
-    handle = C.CDLL(build_native("libszg_anisosample.so", directory=HERE, hashed=[os.path.join(HERE, "anisosample.hip")]))
+    handle = C.CDLL(native.build("anisosample/libszg_anisosample.so"))
     handle.szg_anisosample.restype = C.c_int
     handle.szg_anisosample.argtypes = [C.POINTER(abi.Texture), C.c_void_p, C.c_uint32, C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_uint32]
     return handle

@@ -2,20 +2,18 @@
 corner form of szg::recordCopyImageToImage) through its own interface, from a program built with hipcc
 (tests/texture_display/display_texture.cpp) that draws the viewer quad with UILayer::recordDraw over a hand-made draw-data
 struct - against the Python models, byte for byte."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from syzygy_amd import lib
-from tests.native import build as build_native  # this program has its own Makefile, not a target of tests/Makefile
+from tests import native
 from tests import texture_display_model as tm
 from tests import ui_layer_cases as uc
 from tests import ui_layer_model as um
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "texture_display")
 
 
 @pytest.mark.parametrize("srgb", [1, 0], ids=["srgb", "unorm"])
@@ -25,7 +23,7 @@ def test_texture_display_from_cpp(tmp_path, srgb):
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU; the product path has no CPU fallback")
     lib()  # built and loadable
-    exe = build_native("display_texture", directory=HERE, hashed=[os.path.join(HERE, "display_texture.cpp")])
+    exe = native.build("texture_display/display_texture")
     map_extent, display, frame = (6, 3), (16, 16), (40, 30)
     texels = np.random.default_rng(31).integers(0, 256, (map_extent[1], map_extent[0], 4), dtype=np.uint8)
     texels[..., 3] = 0  # the viewer is opaque all the same: alpha ONE

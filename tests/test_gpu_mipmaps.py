@@ -1,6 +1,6 @@
 """include/szg/mipmaps.h on the GPU, bit for bit against tests/mipmap_model.py: the chain builder (k_mip_downsample) and the
 device sampler of syzygy_amd/csrc/szg_texture.hpp in isolation, called by the test-only kernel of tests/mipsample (built by
-its own make rule with the product's HIPFLAGS)."""
+the DEVICE_LIBS rule of tests/Makefile with the product's HIPFLAGS)."""
 import ctypes as C
 
 import numpy as np

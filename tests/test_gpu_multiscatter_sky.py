@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 
 from tests import multiscatter_sky_model as model
+from tests import native
 from tests import util
-from tests.native import build as build_native  # the C++ caller has its own Makefile, not a target of tests/Makefile
 from tests.test_gpu_parity import gpu, staged  # noqa: F401  (gpu is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -387,13 +387,10 @@ def test_refusals_and_lut_reuse(gpu):
 # 8. the C++ mirror
 # ---------------------------------------------------------------------------
 def test_cpp_set_multi_scattering_equals_the_python_path(gpu, tmp_path):
-    import os
-
     from syzygy_amd import lib
 
     lib()  # built and loadable
-    folder = os.path.join(os.path.dirname(os.path.abspath(__file__)), "multiscatter_sky")
-    exe = build_native("skyview_multiscatter", directory=folder, hashed=[os.path.join(folder, "skyview_multiscatter.cpp")])
+    exe = native.build("multiscatter_sky/skyview_multiscatter")
     prefix = str(tmp_path / "cpp")
     done = subprocess.run([exe, str(gpu.abi.SZG_MULTISCATTER_ADD), prefix], capture_output=True, text=True, timeout=120)
     assert done.returncode == 0 and done.stdout.strip().endswith("ok mode 1"), done.stdout + done.stderr

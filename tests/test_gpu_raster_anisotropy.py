@@ -3,7 +3,6 @@ footprints) and on a wall seen at a grazing angle (x-major ones) the level of de
 geometry predicts; switched off, without a chain and after every refusal the frame is the one it was; and the C++ mirror
 (include/szg/pipelines.hpp) makes the same frame as the Python one, bit for bit."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,14 +10,13 @@ import pytest
 
 from syzygy_amd import abi, lib, meshes
 from tests import mipmap_model as mm
-from tests.native import build as build_native  # the mirror program has its own Makefile, not a target of tests/Makefile
+from tests import native
 from tests import raster_scenes as rs
 from tests import util
 from tests.test_gpu_raster_mipmaps import H, PLANES, PROJECTION, TEX, UV_SCALE, W, Z_FAR, Z_NEAR, Raster, _assert_same_frame, _coded_chain
 from tests.test_raster import _planes_equal
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "anisosample")
 A_MAX = 16.0
 
 
@@ -270,7 +268,7 @@ def test_every_refusal_leaves_the_next_frame_unchanged(gpu, frames):
 def test_the_cpp_mirror_makes_the_same_frame(gpu, frames, tmp_path):
     s = frames["floor"]
     mesh = s["mesh"][0]
-    exe = build_native("raster_anisotropy", directory=HERE, hashed=[os.path.join(HERE, "raster_anisotropy.cpp")])
+    exe = native.build("anisosample/raster_anisotropy")
     mesh.vertices.tofile(tmp_path / "vertices.bin")
     mesh.indices.tofile(tmp_path / "indices.bin")
     mesh._models_np.tofile(tmp_path / "models.bin")

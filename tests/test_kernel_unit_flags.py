@@ -52,7 +52,7 @@ def test_scheduler_options_reach_the_command_lines():
 
 
 def test_resource_usage_targets_name_existing_files():
-    for target in ("resource-usage", "march-resource-usage"):
+    for target in ("resource-usage", "march-resource-usage", "ms-resource-usage"):
         compiles = [c.split() for c in native.commands(target, CSRC) if " -c " in c]
         assert compiles, target
         for words in compiles:

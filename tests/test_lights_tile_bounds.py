@@ -14,9 +14,7 @@ import numpy as np
 
 from syzygy_amd import scene
 from tests import light_tile_model as lt
-from tests.native import build as build_native  # this program has its own Makefile, not a target of tests/Makefile
-
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lights_tiles")
+from tests import native
 
 
 def test_light_tiles_header_is_exported_and_bound():
@@ -36,7 +34,7 @@ def test_light_tiles_header_is_exported_and_bound():
 
 
 def test_a_cleared_bit_means_the_early_out_fires_everywhere_in_the_box(tmp_path):
-    exe = build_native("light_tile_bounds", directory=HERE, hashed=[os.path.join(HERE, "light_tile_bounds.cpp")])
+    exe = native.build("lights_tiles/light_tile_bounds")
     sets = [lt.spot_records(scene.spot_ring(64), 64)] + [lt.spot_records(lt.perturbed_ring(64, seed), 64) for seed in (1, 2, 3)]
     np.concatenate(sets).tofile(tmp_path / "lights.bin")
     done = subprocess.run([exe, str(tmp_path / "lights.bin")], capture_output=True, text=True, timeout=120)

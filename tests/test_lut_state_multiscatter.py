@@ -2,15 +2,11 @@
 (syzygy_amd/csrc/lut_state.hpp: a change of mode, the multi-scattering LUT recorded, the multi-scattering LUT handed out),
 walked on the CPU by tests/multiscatter_sky/lut_state_multiscatter.cpp. tests/test_gpu_multiscatter_sky.py sees the same rules
 through the sentinel of its host-state test."""
-import os
 import subprocess
 
-from tests.native import build as build_native  # this program has its own Makefile, not a target of tests/Makefile
-
-FOLDER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "multiscatter_sky")
+from tests import native
 
 
 def test_multiscatter_events_of_the_lut_state():
-    exe = build_native("lut_state_multiscatter", directory=FOLDER, hashed=[os.path.join(FOLDER, "lut_state_multiscatter.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    out = subprocess.run([native.build("multiscatter_sky/lut_state_multiscatter")], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "lut_state_multiscatter ok" in out.stdout, out.stdout + out.stderr

@@ -2,34 +2,17 @@
 flags and per-unit scheduler options, -Rpass-analysis=kernel-resource-usage). k_composite runs four waves per SIMD without
 scratch and with an LDS queue small enough for four workgroups per CU (4 x 40 960 B = 160 KiB); k_skyview likewise without
 scratch. Only the remark lines are read."""
-import os
-import re
-import subprocess
-
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "syzygy_amd", "csrc")
+from tests import native
+
 FIELDS = {"VGPRs": r"\bVGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)", "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)",
           "lds": r"LDS Size \[bytes/block\]: (\d+)"}
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    done = subprocess.run(["make", "-C", CSRC, "march-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert done.returncode == 0, done.stdout[-4000:]
-    kernels, current = {}, None
-    for line in done.stdout.splitlines():
-        if "remark:" not in line:
-            continue
-        name = re.search(r"Function Name: (\S+)", line)
-        if name:
-            current = kernels.setdefault(name.group(1), {})
-            continue
-        for field, pattern in FIELDS.items():
-            m = re.search(pattern, line)
-            if m and current is not None:
-                current[field] = int(m.group(1))
-    return kernels
+    return native.resource_remarks("march-resource-usage", FIELDS)
 
 
 def one(remarks, fragment):

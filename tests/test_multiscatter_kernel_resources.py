@@ -2,34 +2,17 @@
 syzygy_amd/csrc: the library's flags and the scheduler options of the LUT unit, -Rpass-analysis=kernel-resource-usage):
 k_skyview_ms and k_aerial_lut_ms, one instance per mode, none of them with scratch. Their occupancy is not pinned
 (DESIGN.md §16 states it). Only the remark lines are read."""
-import os
-import re
-import subprocess
-
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "syzygy_amd", "csrc")
+from tests import native
+
 FIELDS = {"VGPRs": r"\bVGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)", "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)",
           "lds": r"LDS Size \[bytes/block\]: (\d+)", "spill": r"VGPRs Spill: (\d+)"}
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    done = subprocess.run(["make", "-C", CSRC, "ms-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert done.returncode == 0, done.stdout[-4000:]
-    kernels, current = {}, None
-    for line in done.stdout.splitlines():
-        if "remark:" not in line:
-            continue
-        name = re.search(r"Function Name: (\S+)", line)
-        if name:
-            current = kernels.setdefault(name.group(1), {})
-            continue
-        for field, pattern in FIELDS.items():
-            m = re.search(pattern, line)
-            if m and current is not None:
-                current[field] = int(m.group(1))
-    return kernels
+    return native.resource_remarks("ms-resource-usage", FIELDS)
 
 
 # (Itanium mangling: k_skyview_ms<1, false> is ...12k_skyview_msILi1ELb0EEE..., k_aerial_lut_ms<2> ...15k_aerial_lut_msILi2EEE...)

@@ -1,5 +1,6 @@
 """tests/native.py: a native test program is rebuilt exactly when the hash of its sources differs from its stamp, whatever
 file times say (on a toy tree), and every target the tests ask for is one tests/Makefile defines."""
+import ast
 import glob
 import os
 import re
@@ -70,13 +71,22 @@ def test_a_failed_build_raises_and_leaves_no_fresh_stamp(toy):
 
 
 def test_the_tests_ask_for_exactly_the_targets_of_the_makefile():
+    """... and in one way: the module is imported and called as native.build with one literal target, so that the search below sees
+    every call; `directory` and `hashed` are for the toy tree above; and tests/Makefile is the only Makefile there is to ask."""
     asked = set()
-    for path in glob.glob(os.path.join(HERE, "*.py")):
+    for path in glob.glob(os.path.join(HERE, "**", "*.py"), recursive=True):
         text = open(path).read()
         calls = re.findall(r'native\.build\("([^"]+)"\)', text)
+        nodes = list(ast.walk(ast.parse(text, path)))
+        imported = [n for n in nodes if isinstance(n, ast.ImportFrom) and (n.module or "").split(".")[-1] == "native"]
+        assert not imported, (path, [n.lineno for n in imported])
         if path != os.path.abspath(__file__):  # the toy's call names a directory too; every other call is a literal target
             assert len(calls) == text.count("native.build("), path
+            keyworded = [n for n in nodes if isinstance(n, ast.Call) and {k.arg for k in n.keywords} & {"directory", "hashed"}]
+            assert not keyworded, (path, [n.lineno for n in keyworded])
         asked |= set(calls)
+    makefiles = glob.glob(os.path.join(HERE, "**", "Makefile"), recursive=True)
+    assert makefiles == [os.path.join(HERE, "Makefile")], makefiles
     variables = native.assignments(os.path.join(HERE, "Makefile"))
     defined = variables["TARGETS"][1]
     while "$(" in defined:
